@@ -5,16 +5,21 @@
 BASELINE.json metric: "images/sec (train step, 256x256x3) at 1/2/4/8 MI355X"; workload =
 configs[1] (batch 16 per GPU, binary, dice loss).  Weak scaling: 16 images per GPU.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 The step is the reference's `model.fit` step as scripts/train.py:227-234 compiles it: forward,
 dice_loss, backward, AdamW and the MeanIoU(2) + dice_coef metric updates.
 
-Prints ONE JSON line on rank 0.  The timed region records nothing.  `roofline` is for the
-dominant kernel, timed with HIP events on its launch stream over a second pass of the same K
-steps; `cpu_baseline` is the torch-CPU restatement of the same train step (oracle/torch_ref.py,
-SURVEY.md 8(d)'s TF-CPU proxy) on a bounded sample, rank 0, N=1 only.
+Prints ONE JSON line on rank 0.  The timed region records nothing.  A plain run does only what
+the headline figure needs: set-up, W warm-up steps, the K timed steps, the line.  `--dump-outputs
+DIR` also writes what the last timed step computed (DIR/<name>.npy, see dump_outputs).
+
+`--full` adds every other measurement, each in a pass of its own after the timed region: the
+per-op breakdown, `roofline` for the dominant kernel (timed with HIP events on its launch stream
+over a second pass of the same K steps), the encoder-block table, the data-parallel all-reduce
+exposure pass (N > 1) and `cpu_baseline`, the torch-CPU restatement of the same train step
+(oracle/torch_ref.py, SURVEY.md 8(d)'s TF-CPU proxy) on a bounded sample, rank 0, N=1 only.
 """
 from __future__ import annotations
 
@@ -299,7 +304,48 @@ def result_line(args, world, dt, loss):
     }
 
 
-def spawn_ranks(n: int) -> int:
+DUMP_BUDGET_BYTES = 60 * 10 ** 6  # all of --dump-outputs' files together stay under 64 MB
+DUMP_SAMPLE_SEED = 2301
+
+
+def bounded_sample(a, max_bytes):
+    """`a` itself if it fits `max_bytes`, else its elements at a fixed (seeded) sorted sample of
+    flat positions, so two runs of the same shapes sample the same places."""
+    import numpy as np
+    if a.nbytes <= max_bytes:
+        return a
+    k = max(int(max_bytes) // a.itemsize, 1)
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, size=k, replace=False))
+    return np.ascontiguousarray(a.reshape(-1)[idx])
+
+
+def dump_outputs(out_dir, model, res, n):
+    """--dump-outputs: what the last timed train step left its caller with, as out_dir/<name>.npy
+    (float32; the confusion counts float64), smallest first against DUMP_BUDGET_BYTES:
+      train_step        the returned vector [loss, dice_coef, iou_coef]
+      bn_moving_stats   the BatchNorm moving means / variances (flat, params.flat_layout order)
+      mean_io_u_confusion  the MeanIoU metric's confusion matrix over warm-up + timed steps
+      weights           the trainable weights after the step's AdamW update (flat)
+      prob              the step's forward output, the class probabilities (N, H, W, classes)
+    An array that does not fit what is left of the budget is written as bounded_sample of it."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    arrays = [("train_step", res.detach().cpu().numpy().astype(np.float32)),
+              ("bn_moving_stats", model.engine.stats.detach().cpu().numpy())]
+    if model.mean_iou is not None:
+        arrays.append(("mean_io_u_confusion", model.mean_iou.confusion_matrix().astype(np.float64)))
+    arrays += [("weights", model.engine.params.detach().cpu().numpy()),
+               ("prob", model.engine.acts(n).prob.detach().cpu().numpy())]
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name, a in arrays:
+        a = bounded_sample(np.ascontiguousarray(a), left)
+        left -= a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def spawn_ranks(n: int, argv) -> int:
     """`bench.py --gpus N` without a launcher: run this same command as N torchrun ranks (one
     process per GPU) in a CHILD process and relay its exit code.  Called before anything touches
     the GPU (no torch / HIP initialisation in this parent), so no process that owns a device
@@ -310,7 +356,7 @@ def spawn_ranks(n: int) -> int:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
-           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + list(argv)
     return subprocess.call(cmd)
 
 
@@ -322,6 +368,12 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=16, help="images per GPU")
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--num-classes", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other measurement (per-op breakdown, roofline "
+                         "pass, encoder-block table, all-reduce exposure pass, CPU baseline); the --no-* options "
+                         "below take single ones out of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-warmup", type=int, default=10, help="CPU baseline warm-up steps (BASELINE.md 3)")
     ap.add_argument("--cpu-steps", type=int, default=10, help="CPU baseline timed steps (median reported)")
@@ -355,13 +407,15 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     return args
 
 
-def main():
-    args = parse_args()
+def main(argv=None):
+    args = parse_args(argv)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(spawn_ranks(args.gpus))
+        sys.exit(spawn_ranks(args.gpus, sys.argv[1:] if argv is None else list(argv)))
 
     import torch
     import torch.distributed as dist
@@ -408,20 +462,6 @@ def main():
         if world > 1:
             dist.barrier()
 
-    # per-op breakdown: one untimed single-stream step with every C-ABI op bracketed by HIP
-    # events on its launch stream; its largest op is the one the roofline object reports
-    breakdown, dominant = None, ROOFLINE_OP
-    if not args.no_roofline:
-        bt = ops.KernelTimer(None)
-        ops.TIMER = bt
-        overlap = model.engine.overlap
-        model.engine.overlap = False  # single stream: per-op times not inflated by the side stream
-        model.train_step(x, y)
-        model.engine.overlap = overlap
-        ops.TIMER = None
-        breakdown = op_breakdown(bt.summary())
-        dominant = breakdown[0]["op"]
-
     # the timed region: K steps, nothing recorded inside it
     barrier()
     torch.cuda.synchronize()
@@ -439,11 +479,30 @@ def main():
     # the MeanIoU of the timed steps (warm-up + K), read before the roofline / all-reduce probe
     # passes below train further, so 1-GPU and N-GPU lines report the same quantity
     miou = model.mean_iou.result()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, res, args.batch)
+
+    # everything below is --full: measurements beside the headline figure, each a pass of its own
+    roofline = args.full and not args.no_roofline
+
+    # per-op breakdown: one untimed single-stream step after the timed region with every C-ABI op bracketed by HIP
+    # events on its launch stream; its largest op is the one the roofline object reports
+    breakdown, dominant = None, ROOFLINE_OP
+    if roofline:
+        bt = ops.KernelTimer(None)
+        ops.TIMER = bt
+        overlap = model.engine.overlap
+        model.engine.overlap = False  # single stream: per-op times not inflated by the side stream
+        model.train_step(x, y)
+        model.engine.overlap = overlap
+        ops.TIMER = None
+        breakdown = op_breakdown(bt.summary())
+        dominant = breakdown[0]["op"]
 
     # roofline pass: the same K steps again (same streams, same overlap) with the dominant
     # kernel's launches bracketed by HIP events on the stream each is issued on
     timer, dt_roof = None, None
-    if not args.no_roofline:
+    if roofline:
         timer = ops.KernelTimer([dominant])
         ops.TIMER = timer
         torch.cuda.synchronize()
@@ -457,7 +516,7 @@ def main():
     # data parallel: a separate pass of K steps measuring the all-reduce time the step exposes on
     # the main stream (from the end of the backward's launches to the last bucket's completion)
     dp_info = None
-    if world > 1:
+    if args.full and world > 1:
         probe = []
         model.dp_probe = probe
         for _ in range(args.steps):
@@ -483,12 +542,12 @@ def main():
             out["data_parallel"] = dp_info
         if model.mean_iou is not None:
             out["mean_io_u"] = round(miou, 6)
-        if not args.no_roofline and world == 1 and args.encoder_batch > 0:
+        if roofline and world == 1 and args.encoder_batch > 0:
             del model
             torch.cuda.empty_cache()
             out["encoder_blocks"] = encoder_block_roofline(args.encoder_batch, args.size, device, x3=not args.no_x3,
                                                            fuse=args.fuse)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.size, args.num_classes, args.batch, args.cpu_warmup,
                                                args.cpu_steps, args.cpu_threads)
         print(json.dumps(out), flush=True)

@@ -341,8 +341,55 @@ def train256b32_fixture():
     return train_big_fixture(256, 32, 21, 91, 15, drop=0.2)
 
 
+PART_BYTES = 900 * 1024  # no committed file over 1 MiB: a larger fixture is stored in parts
+
+
+def part_paths(name):
+    """The files of a fixture stored in parts: NAME.npz -> NAME.part0.npz, NAME.part1.npz, ..."""
+    import glob
+    stem = os.path.join(HERE, name[:-len(".npz")])
+    return sorted(glob.glob(glob.escape(stem) + ".part*.npz"),
+                  key=lambda p: int(p[len(stem) + len(".part"):-len(".npz")]))
+
+
 def write(name, d):
-    np.savez_compressed(os.path.join(HERE, name), **{k.replace("/", "|"): v for k, v in d.items()})
+    """Save fixture `name` (keys with "/" as "|").  One that compresses to more than PART_BYTES
+    is split by keys, in order, into NAME.partK.npz files of at most that size; load() joins them."""
+    import zipfile
+    d = {k.replace("/", "|"): v for k, v in d.items()}
+    path = os.path.join(HERE, name)
+    for old in part_paths(name):
+        os.remove(old)
+    np.savez_compressed(path, **d)
+    if os.path.getsize(path) <= PART_BYTES:
+        return
+    with zipfile.ZipFile(path) as z:  # (zip headers: about 2 x (40 + name) bytes per entry on top of the data)
+        cost = {i.filename[:-len(".npy")]: i.compress_size + 2 * (64 + len(i.filename)) for i in z.infolist()}
+    os.remove(path)
+    groups, size = [[]], 0
+    for k in d:
+        if groups[-1] and size + cost[k] > PART_BYTES:
+            groups.append([])
+            size = 0
+        groups[-1].append(k)
+        size += cost[k]
+    for n, keys in enumerate(groups):
+        part = f"{path[:-len('.npz')]}.part{n}.npz"
+        np.savez_compressed(part, **{k: d[k] for k in keys})
+        assert os.path.getsize(part) <= 1 << 20, (part, os.path.getsize(part))
+
+
+def load(name):
+    """Fixture `name` as {key: array} (keys with "/" restored), from NAME.npz or its parts."""
+    path = os.path.join(HERE, name)
+    paths = [path] if os.path.exists(path) else part_paths(name)
+    if not paths:
+        raise FileNotFoundError(path)
+    out = {}
+    for p in paths:
+        with np.load(p, allow_pickle=False) as z:
+            out.update({k.replace("|", "/"): z[k] for k in z.files})
+    return out
 
 
 BIG = {"fwd256.npz": fwd256_fixture, "fwd512.npz": fwd512_fixture, "fwd21.npz": fwd21_fixture,
@@ -355,7 +402,7 @@ BIG = {"fwd256.npz": fwd256_fixture, "fwd512.npz": fwd512_fixture, "fwd21.npz": 
 if __name__ == "__main__" and len(sys.argv) > 1:  # regenerate only the named fixtures
     for nm in sys.argv[1:]:
         write(nm, BIG[nm]())
-        print(nm, os.path.getsize(os.path.join(HERE, nm)))
+        print(nm, [os.path.getsize(p) for p in part_paths(nm) or [os.path.join(HERE, nm)]])
 elif __name__ == "__main__":
     for nm, fn in BIG.items():
         write(nm, fn())

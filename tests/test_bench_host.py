@@ -30,6 +30,35 @@ def test_single_gpu_line_contract():
     assert out["config"]["workload"].startswith("configs[1]") and out["config"]["parallelism"] == "dp1"
 
 
+def test_plain_run_is_the_default_and_full_is_opt_in():
+    a = _args("--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    out = bench.result_line(a, 1, 0.07, 0.5)
+    assert out["steps"] == 7 and out["ms_per_step"] == pytest.approx(10.0)
+    a = _args("--full", "--dump-outputs", "somewhere")
+    assert a.full is True and a.dump_outputs == "somewhere"
+    with pytest.raises(SystemExit):
+        _args("--steps", "0")
+
+
+def test_inputs_are_identical_from_run_to_run():
+    for ncls in (1, 3):
+        x0, y0 = bench.synthetic_batch(2, 32, 32, ncls, 2301, "cpu")
+        x1, y1 = bench.synthetic_batch(2, 32, 32, ncls, 2301, "cpu")
+        assert torch.equal(x0, x1) and torch.equal(y0, y1)
+        assert x0.shape == (2, 32, 32, 3) and y0.shape == (2, 32, 32, ncls)
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    import numpy as np
+    a = np.arange(10000, dtype=np.float32).reshape(100, 100)
+    assert bench.bounded_sample(a, a.nbytes) is a
+    s0, s1 = bench.bounded_sample(a, 4000), bench.bounded_sample(a.copy(), 4000)
+    assert s0.nbytes <= 4000 and s0.dtype == np.float32 and s0.shape == (1000,)
+    assert np.array_equal(s0, s1) and len(np.unique(s0)) == 1000 and np.all(np.diff(s0) > 0)
+    assert bench.DUMP_BUDGET_BYTES <= 64 * 10 ** 6
+
+
 class _FakeDist:
     """The slice of torch.distributed GradBucketer uses, for a world of 8 (no rendezvous)."""
 

@@ -75,7 +75,7 @@ def test_bench_gpus_flag_spawns_ranks():
     if torch.cuda.device_count() < 2:
         env["UNET_DP_ONE_DEVICE"] = "1"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-roofline", "--encoder-batch", "0"]
+           "--full", "--no-cpu-baseline", "--no-roofline", "--encoder-batch", "0"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
