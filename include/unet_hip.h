@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UNET_ABI_VERSION 12
+#define UNET_ABI_VERSION 13
 
 typedef void* unet_stream_t; /* hipStream_t */
 
@@ -523,6 +523,59 @@ int unet_adamw_step(float* param, const float* grad, float* m, float* v,
                     int64_t count, float lr, float weight_decay, float beta1,
                     float beta2, float eps, float alpha, float grad_scale,
                     unet_stream_t stream);
+
+/* ----- Frozen half-precision inference (ABI 13) ----------------------------------------------
+ * The deployment step of the reference (scripts/tensorflow_lite/convert_to_tflite.py --float16):
+ * a trained model frozen into a half-precision inference artefact.  BatchNormalization
+ * (model/u_net.py:22-23) is folded into the pointwise weights on the host (unet_amd/frozen.py:
+ * pw' = pointwise_kernel * gamma / sqrt(moving_variance + eps), bias' = beta - moving_mean * scale),
+ * so a conv_block is depthwise 3x3 -> pointwise -> + bias' -> ReLU.  Activations are NHWC fp16
+ * (passed as unsigned short), dense, 16-byte aligned, and are stored ALREADY ACTIVATED: no
+ * BN / ReLU / max-pool views exist on this path.  Products run on v_mfma_f32_32x32x16_f16 with fp32
+ * accumulators.  Rounding to fp16 (nearest even) happens at exactly: the folded pointwise and
+ * upsample kernels (host), each block's depthwise output, each block's output after bias + ReLU,
+ * each upsample's output after bias.  Everything else (the image, the image block, depthwise
+ * sums, accumulators, biases, the head) is fp32.                                               */
+enum { UNET_F16_VIEW_PLAIN = 0, /* x = src0 (n, h, w, c0)                     */
+       UNET_F16_VIEW_CONCAT = 1 /* x = [src0 (c0) | src1 (c1)] (u_net.py:95-96) */ };
+typedef struct unet_f16_view {
+    int32_t mode;
+    int32_t c0;          /* multiple of 16 */
+    int32_t c1;          /* CONCAT only (multiple of 16), else 0 */
+    int32_t reserved0;
+    const unsigned short* src0;
+    const unsigned short* src1;
+} unet_f16_view;
+
+/* The image block (enc1_block1, model/u_net.py:62) on the caller's UNPADDED fp32 image
+ * (n, h, w, cin <= 4): out (n, h, w, cout) fp16 = relu(depthwise3x3(x) . pw_folded + bias), all
+ * in fp32 up to the output rounding.  dw_kernel (3, 3, cin, 1), pw_folded (cin, cout) fp32,
+ * cout % 8 == 0.                                                                               */
+int unet_f16_image_block(const float* x, int n, int h, int w, int cin, const float* dw_kernel,
+                         int cout, const float* pw_folded, const float* bias,
+                         unsigned short* out, unet_stream_t stream);
+/* A folded conv_block (model/u_net.py:5-26): out (n, h, w, cout) fp16 =
+ * relu(fp16(depthwise3x3(x)) . pw_t^T + bias).  dw_kernel is the Keras (3, 3, C, 1) fp32 kernel,
+ * C = c0 + c1; pw_t the folded pointwise kernel as fp16 [cout][C] (k contiguous); bias fp32;
+ * cout % 32 == 0.  out_pool (optional, (n, h/2, w/2, cout), h and w even): MaxPooling2D((2,2))
+ * (u_net.py:69) of out, written by the same launch.  route selects how taps are fetched:
+ * 0 = auto, 1 = rows (any shape: taps from global memory under bounds predicates), 2 = tile
+ * (8 x 16-pixel tiles with an fp16 halo in LDS; needs h % 8 == 0 and w % 16 == 0, refused
+ * otherwise); auto takes tile where it applies.  Both give bitwise the same result.           */
+int unet_f16_sepconv(const unet_f16_view* x, int n, int h, int w, const float* dw_kernel,
+                     int cout, const unsigned short* pw_t, const float* bias,
+                     unsigned short* out, unsigned short* out_pool, int route,
+                     unet_stream_t stream);
+/* Conv2DTranspose(f, 2, strides=2) (u_net.py:88-94) on fp16: x (n, h, w, cin), kernel the Keras
+ * (2, 2, cout, cin) layout rounded to fp16, bias fp32; out (n, 2h, 2w, cout) fp16 = x . k + bias
+ * (no activation).  cin % 16 == 0, cout % 8 == 0.                                              */
+int unet_f16_conv_transpose2x2(const unsigned short* x, int n, int h, int w, int cin, int cout,
+                               const unsigned short* kernel, const float* bias,
+                               unsigned short* out, unet_stream_t stream);
+/* Output layer (u_net.py:105-112) on an fp16 input (n, h, w, cin), cin % 8 == 0: fp32 kernel
+ * (1, 1, cin, ncls) and bias, fp32 prob (n, h, w, ncls) = sigmoid (ncls == 1) or softmax.      */
+int unet_f16_head(const unsigned short* x, int n, int h, int w, int cin, int ncls,
+                  const float* kernel, const float* bias, float* prob, unet_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,208 @@
+"""The frozen fp16 network end to end (UNetModel.freeze() -> FrozenUNet) against the float64 oracle.
+
+Random-weight probabilities span only ~4e-3 and hide layer bugs, so the gate is PER LAYER: for
+every name activation() serves and for prob,
+
+    max |gpu - f64|  <=  max(2 max |emu - f64|, 2^-11 max |f64|)
+
+where emu is the NumPy emulator with the kernels' four rounding points (tests/f16_emulation.py),
+computed here on the same inputs: the reference sets the yardstick, not the code under test.  A
+second realisation of the same rounding points (3e-7 relative perturbation before each rounding)
+stays within 1.02x of the emulator's own error on every layer, so the factor 2 has room for the
+device's fp32 sums while a real defect (one zeroed bias is 5x .. 300x at its own layer) is far
+outside.  With UNET_PARITY_LOG set, every layer's gpu and emu error is appended to that file.
+"""
+import functools
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, "golden"))
+sys.path.insert(0, os.path.join(os.path.dirname(HERE), "unet-image-segmentation_amd", "scripts"))
+
+import f16_emulation as E  # noqa: E402
+import make_golden as MG  # noqa: E402
+from unet_amd import frozen  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+F = (64, 128, 256, 512)
+# name -> (classes, input shape, weight seed, input seed, use_batch_norm)
+CASES = {
+    "c1_2x32x32": (1, (2, 32, 32, 3), 11, 21, True),
+    "c3_3x48x32": (3, (3, 48, 32, 3), 2301, 7, True),   # tile levels 48x32, 24x16; rows 12x8, 6x4, 3x2
+    "c1_1x16x16": (1, (1, 16, 16, 3), 11, 21, True),    # the bottleneck is 1x1
+    "nobn_2x32x32": (1, (2, 32, 32, 3), 11, 21, False),  # case 1 as a no-BN model: the bias route
+}
+
+
+def _weights(ncls, wseed, use_bn):
+    w = MG.model_weights(ncls, F, wseed)
+    if use_bn:
+        return w
+    # the same function without BatchNorm: pointwise_kernel = pk * scale, bias = shift
+    ex = frozen.fold_exact(w, ncls, True, F)
+    out = {k: v for k, v in w.items() if "_bn/" not in k}
+    for b in frozen.block_names(F):
+        out[f"{b}_sepconv/pointwise_kernel"] = ex[f"{b}_sepconv/pointwise_kernel"]
+        out[f"{b}_sepconv/bias"] = ex[f"{b}_sepconv/bias"]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(case):
+    """(weights, x, float64 oracle activations, emulator activations), computed once per case."""
+    ncls, shape, wseed, xseed, use_bn = CASES[case]
+    w = _weights(ncls, wseed, use_bn)
+    x = MG.U(xseed, shape)
+    ref = E.oracle_activations(w, x, ncls, F, use_bn)
+    emu = E.forward(frozen.fold_weights(w, ncls, use_bn, F), x, ncls, F)
+    return w, x, ref, emu
+
+
+def _frozen(case):
+    ncls, shape, _, _, use_bn = CASES[case]
+    w, x, _, _ = _reference(case)
+    net = frozen.FrozenUNet(frozen.fold_weights(w, ncls, use_bn, F), shape[1:], ncls, F, "cuda:0")
+    return net, torch.as_tensor(x.astype(np.float32), device="cuda:0")
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_every_layer_within_the_emulator_gate(case):
+    net, xt = _frozen(case)
+    _, _, ref, emu = _reference(case)
+    prob = net.forward(xt, keep_activations=True)
+    torch.cuda.synchronize()
+    got = {name: net.activation(name).cpu().numpy().astype(np.float64) for name in frozen.activation_names(F)}
+    got["prob"] = prob.cpu().numpy().astype(np.float64)
+    assert prob.dtype == torch.float32 and set(got) == set(ref)
+    rows, bad = [], []
+    for name in ref:
+        assert got[name].shape == ref[name].shape, name
+        g = float(np.abs(got[name] - ref[name]).max())
+        e = float(np.abs(emu[name] - ref[name]).max())
+        mx = float(np.abs(ref[name]).max())
+        gate = max(2.0 * e, 2.0 ** -11 * mx)
+        rows.append({"case": case, "layer": name, "gpu": g, "emu": e, "max": mx, "gate": gate})
+        if not g <= gate:
+            bad.append((name, g, gate))
+    log = os.environ.get("UNET_PARITY_LOG")
+    if log:
+        with open(log, "a") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+    print(case, "worst gpu / gate", max(r["gpu"] / r["gate"] for r in rows))
+    assert not bad, bad
+    # the ping-pong forward (no kept activations) computes the same probabilities
+    assert torch.equal(net.forward(xt), prob)
+    with pytest.raises(KeyError):
+        net.activation("enc5_pool")
+
+
+def test_activation_needs_a_kept_forward():
+    net, xt = _frozen("c1_1x16x16")
+    net.forward(xt)
+    with pytest.raises(RuntimeError, match="keep_activations"):
+        net.activation("bneck_block2")
+    with pytest.raises(ValueError, match="expected input"):
+        net.forward(xt[:, :8])
+
+
+def test_predict_in_chunks_equals_one_call():
+    net, xt = _frozen("c3_3x48x32")
+    x = xt.cpu().numpy()
+    whole = net.predict(x)
+    parts = net.predict(x, batch_size=2)
+    assert isinstance(whole, np.ndarray) and whole.dtype == np.float32 and whole.shape == (3, 48, 32, 3)
+    assert np.array_equal(whole.view(np.uint32), parts.view(np.uint32))
+    dev = net.predict(xt)
+    assert isinstance(dev, torch.Tensor) and dev.is_cuda and np.array_equal(dev.cpu().numpy(), whole)
+    np.testing.assert_allclose(whole.sum(axis=-1), 1.0, atol=1e-5)
+
+
+@pytest.fixture(scope="module")
+def model():
+    from unet_amd.model import UNetModel
+    m = UNetModel((32, 32, 3), 1, dropout_rate=0.0, device="cuda:0")
+    m.engine.set_weights_dict({k: v.astype(np.float32) for k, v in MG.model_weights(1, F, 11).items()})
+    return m
+
+
+def test_freeze_matches_the_source_model_and_snapshots_it(model):
+    from unet_amd.optim import AdamW
+    x = MG.U(21, (2, 32, 32, 3)).astype(np.float32)
+    fz = model.freeze()
+    assert isinstance(fz, frozen.FrozenUNet) and fz.dtype == "float16"
+    with pytest.raises(ValueError, match="float16"):
+        model.freeze(dtype="bfloat16")
+    before = fz.predict(x)
+    p32 = model.predict(x)
+    _, _, ref, emu = _reference("c1_2x32x32")
+    # (fp32 weights here, float64 in the reference: the gap is far below the fp16 gate)
+    gate = max(2.0 * np.abs(emu["prob"] - ref["prob"]).max(), 2.0 ** -11 * np.abs(ref["prob"]).max())
+    assert np.abs(before - ref["prob"]).max() <= gate
+    assert np.abs(before - p32).max() <= 2 * gate
+    # a train step on the source model leaves the frozen copy bitwise unchanged
+    model.compile(AdamW(learning_rate=1e-2), "dice_loss")
+    y = (MG.U(22, (2, 32, 32, 1)) > 0.5).astype(np.float32)
+    model.train_step(x, y)
+    torch.cuda.synchronize()
+    assert not np.array_equal(model.predict(x), p32)
+    assert np.array_equal(fz.predict(x).view(np.uint32), before.view(np.uint32))
+
+
+def test_save_load_reproduces_predict(model, tmp_path):
+    x = MG.U(21, (2, 32, 32, 3)).astype(np.float32)
+    fz = model.freeze()
+    path = str(tmp_path / "frozen_model.h5")  # written to the exact path
+    fz.save(path)
+    assert os.path.isfile(path) and frozen.is_frozen_file(path)
+    back = frozen.FrozenUNet.load(path, device="cuda:0")
+    assert (back.h, back.w, back.c, back.num_classes, back.filters) == (32, 32, 3, 1, F)
+    assert np.array_equal(back.predict(x).view(np.uint32), fz.predict(x).view(np.uint32))
+
+
+def test_inference_cli_with_a_frozen_model(tmp_path):
+    """scripts/inference.py --model <frozen file> writes the mask the fp32 model writes, on an
+    image whose fp32 probabilities all lie farther than 1e-3 from the threshold (asserted)."""
+    import convert_to_frozen
+    import inference
+    from PIL import Image
+    from unet_amd.model import UNetModel
+    m = UNetModel((256, 256, 3), 1, dropout_rate=0.0, device="cuda:0")
+    w = {k: v.astype(np.float32) for k, v in MG.model_weights(1, F, 11).items()}
+    # spread the random-weight probabilities (~4e-3 wide as drawn) around 0.5
+    w["output_mask/kernel"] = w["output_mask/kernel"] * 8.0
+    w["output_mask/bias"] = np.full(1, -1.85, np.float32)
+    m.engine.set_weights_dict(w)
+    # black | white halves: the float64 oracle puts 255 border pixels 7e-3 above all the others
+    # (the widest gap of the sorted probabilities), 20x the frozen network's 1.6e-4 error there
+    img = np.zeros((256, 256, 3), np.uint8)
+    img[:, 128:] = 255
+    png = str(tmp_path / "two_tone.png")
+    Image.fromarray(img).save(png)
+    x, _, _, _ = inference.load_and_preprocess_image(png, 256, 256)
+    p = m.predict(x)[0, ..., 0].astype(np.float64)
+    s = np.sort(p.ravel())
+    lo, hi = 16, s.size - 16  # at least 16 pixels on either side of the threshold
+    i = lo + int(np.argmax(np.diff(s[lo:hi])))
+    thr = 0.5 * (s[i] + s[i + 1])
+    assert 0.0 < thr < 1.0
+    assert np.abs(p - thr).min() > 1e-3, ("no clear gap in the fp32 probabilities", float(s[i + 1] - s[i]))
+    plain, frz = str(tmp_path / "w.npz"), str(tmp_path / "w_f16.npz")
+    m.save_weights(plain)
+    assert convert_to_frozen.main([plain, frz, "--float16"]) == 0
+    masks = []
+    for model_file in (plain, frz):
+        om = str(tmp_path / (os.path.basename(model_file) + "_mask.png"))
+        inference.main([png, "--model", model_file, "--output_mask", om,
+                        "--output_cropped", str(tmp_path / "crop.png"), "--threshold", repr(float(thr))])
+        masks.append(np.asarray(Image.open(om)))
+    assert masks[0].shape == (256, 256) and set(np.unique(masks[0]).tolist()) == {0, 255}
+    assert np.array_equal(masks[0], masks[1])

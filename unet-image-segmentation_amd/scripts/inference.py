@@ -109,10 +109,15 @@ def main(argv=None):
         sys.exit(1)
     print(f"Loading model from {args.model} ...")
     try:
-        from model.u_net import U_NET
-        model = U_NET((IMG_HEIGHT, IMG_WIDTH, 3), 1)
-        model.load_weights(args.model)
-        print("Model loaded successfully.")
+        from unet_amd.frozen import FrozenUNet, is_frozen_file
+        if is_frozen_file(args.model):  # an artefact of scripts/convert_to_frozen.py
+            model = FrozenUNet.load(args.model)
+            print("Frozen float16 model loaded successfully.")
+        else:
+            from model.u_net import U_NET
+            model = U_NET((IMG_HEIGHT, IMG_WIDTH, 3), 1)
+            model.load_weights(args.model)
+            print("Model loaded successfully.")
     except Exception as e:
         print("\n--- Error loading model ---")
         print(f"{e}")

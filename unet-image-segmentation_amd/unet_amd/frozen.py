@@ -1,0 +1,333 @@
+"""Frozen half-precision inference: the engine's counterpart of the reference's deployment step
+(scripts/tensorflow_lite/convert_to_tflite.py --float16).
+
+`fold_weights` is pure NumPy (float64): BatchNormalization (model/u_net.py:22-23, eps 1e-3) folds
+into the pointwise kernel and a bias, and the matrix-core operands are rounded to fp16.
+`FrozenUNet` runs the folded network on the fp16 kernels of csrc/frozen.hip: activations travel
+as fp16, already activated (ReLU at the producer, max-pool written by the producer), the
+pointwise GEMMs are one fp16 MFMA product per step with fp32 accumulation.
+
+Rounding to fp16 (nearest even) happens at exactly four places: the folded pointwise / upsample
+kernels (here), each block's depthwise output, each block's output after bias + ReLU, each
+upsample's output after bias.  Everything else is fp32.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+
+BN_EPS = 1e-3  # keras.layers.BatchNormalization default
+F16_MAX = 65504.0
+FORMAT_VERSION = 1
+MARKER = "__frozen_unet__"
+IMAGE_BLOCK = "enc1_block1"
+
+
+def block_names(filters: Sequence[int]):
+    """The conv blocks in forward order."""
+    n = len(filters)
+    names = []
+    for i in range(n):
+        names += [f"enc{i + 1}_block1", f"enc{i + 1}_block2"]
+    names += ["bneck_block1", "bneck_block2"]
+    for i in range(n):
+        names += [f"dec{n - i}_block1", f"dec{n - i}_block2"]
+    return names
+
+
+def activation_names(filters: Sequence[int]):
+    """Every name FrozenUNet.activation() serves."""
+    n = len(filters)
+    return (block_names(filters) + [f"dec{n - i}_upsample" for i in range(n)]
+            + [f"enc{i + 1}_pool" for i in range(n)])
+
+
+def _checked(name: str, a: np.ndarray) -> np.ndarray:
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"{name}: folded values are not finite")
+    if a.size and np.abs(a).max() > F16_MAX:
+        raise ValueError(f"{name}: folded magnitude {np.abs(a).max():.6g} exceeds the fp16 range ({F16_MAX:g})")
+    return a
+
+
+def fold_exact(weights: Dict[str, np.ndarray], num_classes: int, use_batch_norm: bool,
+               filters: Sequence[int]) -> Dict[str, np.ndarray]:
+    """The frozen network's variables in float64, before any rounding: per block
+    `depthwise_kernel`, `pointwise_kernel` (BatchNorm scale folded in) and `bias`; the upsample and
+    head variables unchanged.  The same function as the source model's inference forward."""
+    filters = tuple(int(f) for f in filters)
+    out: Dict[str, np.ndarray] = {}
+
+    def w64(name):
+        if name not in weights:
+            raise ValueError(f"missing variable {name}")
+        return np.asarray(weights[name], np.float64)
+
+    for b in block_names(filters):
+        pk = w64(f"{b}_sepconv/pointwise_kernel")
+        if use_batch_norm:
+            scale = w64(f"{b}_bn/gamma") / np.sqrt(w64(f"{b}_bn/moving_variance") + BN_EPS)
+            pw = pk * scale
+            bias = w64(f"{b}_bn/beta") - w64(f"{b}_bn/moving_mean") * scale
+        else:
+            pw, bias = pk, w64(f"{b}_sepconv/bias")
+        out[f"{b}_sepconv/depthwise_kernel"] = w64(f"{b}_sepconv/depthwise_kernel")
+        out[f"{b}_sepconv/pointwise_kernel"] = pw
+        out[f"{b}_sepconv/bias"] = bias
+    for i in range(len(filters)):
+        s = f"dec{len(filters) - i}_upsample"
+        out[f"{s}/kernel"] = w64(f"{s}/kernel")
+        out[f"{s}/bias"] = w64(f"{s}/bias")
+    out["output_mask/kernel"] = w64("output_mask/kernel")
+    out["output_mask/bias"] = w64("output_mask/bias")
+    if out["output_mask/kernel"].shape[-1] != num_classes:
+        raise ValueError(f"output_mask/kernel has {out['output_mask/kernel'].shape[-1]} classes, "
+                         f"expected {num_classes}")
+    return out
+
+
+def fold_weights(weights: Dict[str, np.ndarray], num_classes: int, use_batch_norm: bool,
+                 filters: Sequence[int]) -> Dict[str, np.ndarray]:
+    """Fold a trained model's variables (Keras names and layouts) into the frozen network's:
+    per block `depthwise_kernel` (fp32), `pointwise_kernel` (fp16; fp32 for the image block) and
+    `bias` (fp32); `decN_upsample/kernel` fp16 with an fp32 bias; the head in fp32.  Computed in
+    float64 (fold_exact), then rounded.  ValueError names the variable whose folded values are
+    not finite or exceed the fp16 range, and refuses widths that are not multiples of 32."""
+    filters = tuple(int(f) for f in filters)
+    for f in filters:
+        if f <= 0 or f % 32:
+            raise ValueError(f"filters {filters}: the fp16 kernels need widths that are multiples of 32, got {f}")
+    half = {f"{b}_sepconv/pointwise_kernel" for b in block_names(filters) if b != IMAGE_BLOCK}
+    half |= {f"dec{i + 1}_upsample/kernel" for i in range(len(filters))}
+    return {name: _checked(name, a).astype(np.float16 if name in half else np.float32)
+            for name, a in fold_exact(weights, num_classes, use_batch_norm, filters).items()}
+
+
+# ---------------------------------------------------------------------- the artefact ---
+def to_archive(folded: Dict[str, np.ndarray], input_size, num_classes: int, filters) -> Dict[str, np.ndarray]:
+    """The arrays of a frozen .npz: the folded variables in Keras layouts (':' for '/'), the
+    geometry, the dtype, a format version and the marker key."""
+    arc = {k.replace("/", ":"): np.ascontiguousarray(v) for k, v in folded.items()}
+    arc[MARKER] = np.asarray(1, np.int32)
+    arc["format_version"] = np.asarray(FORMAT_VERSION, np.int32)
+    arc["dtype"] = np.asarray("float16")
+    arc["input_size"] = np.asarray(tuple(int(v) for v in input_size), np.int32)
+    arc["num_classes"] = np.asarray(int(num_classes), np.int32)
+    arc["filters"] = np.asarray(tuple(int(f) for f in filters), np.int32)
+    return arc
+
+
+_META = (MARKER, "format_version", "dtype", "input_size", "num_classes", "filters")
+
+
+def from_archive(arc) -> Tuple[Dict[str, np.ndarray], dict]:
+    """Inverse of to_archive over any mapping of arrays (an open NpzFile included)."""
+    keys = list(arc.files) if hasattr(arc, "files") else list(arc)
+    if MARKER not in keys:
+        raise ValueError("not a frozen U-Net file (marker key missing)")
+    version = int(arc["format_version"])
+    if version != FORMAT_VERSION:
+        raise ValueError(f"frozen file format {version}, this build reads {FORMAT_VERSION}")
+    dtype = str(arc["dtype"])
+    if dtype != "float16":
+        raise ValueError(f"frozen file dtype {dtype!r}: only float16 exists")
+    meta = {"input_size": tuple(int(v) for v in arc["input_size"]), "num_classes": int(arc["num_classes"]),
+            "filters": tuple(int(v) for v in arc["filters"]), "dtype": dtype}
+    folded = {k.replace(":", "/"): np.asarray(arc[k]) for k in keys if k not in _META}
+    return folded, meta
+
+
+def save_archive(path, arc: Dict[str, np.ndarray]) -> None:
+    with open(path, "wb") as f:  # the exact path given (np.savez would append .npz to a name)
+        np.savez(f, **arc)
+
+
+def load_archive(path) -> Tuple[Dict[str, np.ndarray], dict]:
+    with open(path, "rb") as f, np.load(f, allow_pickle=False) as z:
+        return from_archive(z)
+
+
+def is_frozen_file(path) -> bool:
+    """True when `path` is an .npz carrying the frozen marker (any other file: False)."""
+    try:
+        with open(path, "rb") as f, np.load(f, allow_pickle=False) as z:
+            return MARKER in z.files
+    except Exception:  # unreadable, not a zip archive, a bare .npy, ...: the caller's loader reports it
+        return False
+
+
+# ------------------------------------------------------------------------ the network ---
+class FrozenUNet:
+    """A frozen fp16 copy of a U-Net: inference only, its own weights."""
+
+    def __init__(self, folded: Dict[str, np.ndarray], input_size, num_classes: int, filters, device=None):
+        import torch
+
+        from . import _lib as L
+        from .params import check_input_size
+        if not torch.cuda.is_available():
+            raise RuntimeError("FrozenUNet needs a HIP device (MI355X); there is no CPU execution path")
+        L.load()
+        self.filters = tuple(int(f) for f in filters)
+        self.h, self.w, self.c = check_input_size(input_size, len(self.filters))
+        if self.c > 4:
+            raise ValueError(f"the image block takes at most 4 input channels, got {self.c}")
+        self.num_classes = int(num_classes)
+        self.dtype = "float16"
+        self.device = torch.device(device if device is not None else "cuda")
+        self.folded = {k: np.array(v, copy=True) for k, v in folded.items()}  # Keras layouts, host
+        self._dev: Dict[str, "torch.Tensor"] = {}
+        self._pack()
+        self._bufs: Dict[int, dict] = {}
+        self._kept: Dict[str, "torch.Tensor"] = {}
+
+    # ------------------------------------------------------------------ construction ---
+    @classmethod
+    def from_model(cls, model, dtype: str = "float16") -> "FrozenUNet":
+        if dtype != "float16":
+            raise ValueError(f"freeze(dtype={dtype!r}): float16 is the only frozen format")
+        e = model.engine
+        folded = fold_weights(e.get_weights_dict(), e.num_classes, e.use_bn, e.filters)
+        return cls(folded, (e.h, e.w, e.c), e.num_classes, e.filters, e.device)
+
+    def _pack(self):
+        """Device operands: pointwise kernels as [cout][cin] fp16 (k contiguous, the MFMA B
+        layout), everything else flat in its Keras layout."""
+        import torch
+
+        def put(a):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+
+        f = self.folded
+        for b in block_names(self.filters):
+            pk = f[f"{b}_sepconv/pointwise_kernel"][0, 0]
+            self._dev[f"{b}/dw"] = put(f[f"{b}_sepconv/depthwise_kernel"].astype(np.float32).reshape(-1))
+            self._dev[f"{b}/pw"] = put(pk.astype(np.float32) if b == IMAGE_BLOCK else pk.T.astype(np.float16))
+            self._dev[f"{b}/bias"] = put(f[f"{b}_sepconv/bias"].astype(np.float32))
+        for i in range(len(self.filters)):
+            s = f"dec{i + 1}_upsample"
+            self._dev[f"{s}/k"] = put(f[f"{s}/kernel"].astype(np.float16))
+            self._dev[f"{s}/bias"] = put(f[f"{s}/bias"].astype(np.float32))
+        self._dev["head/k"] = put(f["output_mask/kernel"].astype(np.float32).reshape(-1))
+        self._dev["head/bias"] = put(f["output_mask/bias"].astype(np.float32))
+
+    # ---------------------------------------------------------------------- file i/o ---
+    def archive(self) -> Dict[str, np.ndarray]:
+        return to_archive(self.folded, (self.h, self.w, self.c), self.num_classes, self.filters)
+
+    def save(self, path) -> None:
+        save_archive(path, self.archive())
+
+    @classmethod
+    def load(cls, path, device=None) -> "FrozenUNet":
+        folded, meta = load_archive(path)
+        return cls(folded, meta["input_size"], meta["num_classes"], meta["filters"], device)
+
+    # ----------------------------------------------------------------------- forward ---
+    def _buffers(self, n: int) -> dict:
+        """Per batch size: the four skips, their pooled copies and one pair of ping-pong buffers."""
+        import torch
+        b = self._bufs.get(n)
+        if b is None:
+            def e(*shape):
+                return torch.empty(shape, dtype=torch.float16, device=self.device)
+            b = {"skip": [], "pool": []}
+            h, w = self.h, self.w
+            for f in self.filters:
+                b["skip"].append(e(n, h, w, f))
+                b["pool"].append(e(n, h // 2, w // 2, f))
+                h, w = h // 2, w // 2
+            big = n * self.h * self.w * self.filters[0]  # the largest activation (full resolution)
+            b["ping"] = [e(big), e(big)]
+            self._bufs[n] = b
+        return b
+
+    def release_buffers(self):
+        self._bufs.clear()
+        self._kept.clear()
+
+    def forward(self, x, keep_activations: bool = False):
+        """x: fp32 device tensor (N, H, W, C).  Returns fp32 probabilities (N, H, W, classes) in a
+        new tensor.  keep_activations: every layer's fp16 output stays readable by activation()."""
+        import torch
+
+        from . import ops
+        from .ops import F16View
+        if x.dim() != 4 or tuple(x.shape[1:]) != (self.h, self.w, self.c):
+            raise ValueError(f"expected input (N, {self.h}, {self.w}, {self.c}), got {tuple(x.shape)}")
+        n = int(x.shape[0])
+        d, fl = self._dev, self.filters
+        self._kept = {}
+        bufs = None if keep_activations else self._buffers(n)
+        state = {"cur": 0}
+
+        def new(name, h, w, c, fixed=None):
+            if keep_activations:
+                t = torch.empty((n, h, w, c), dtype=torch.float16, device=self.device)
+                self._kept[name] = t
+                return t
+            if fixed is not None:
+                return fixed
+            state["cur"] ^= 1
+            return bufs["ping"][state["cur"]][:n * h * w * c].view(n, h, w, c)
+
+        def block(name, view, h, w, cout, out, pool=None):
+            ops.f16_sepconv(view, n, h, w, d[f"{name}/dw"], cout, d[f"{name}/pw"], d[f"{name}/bias"], out, pool)
+            return out
+
+        h, w = self.h, self.w
+        skips = []
+        a = None
+        for i, f in enumerate(fl):
+            s = f"enc{i + 1}"
+            out = new(f"{s}_block1", h, w, f)
+            if i == 0:
+                ops.f16_image_block(x, n, h, w, self.c, d[f"{s}_block1/dw"], f, d[f"{s}_block1/pw"],
+                                    d[f"{s}_block1/bias"], out)
+            else:
+                block(f"{s}_block1", F16View.plain(a), h, w, f, out)
+            skip = new(f"{s}_block2", h, w, f, None if bufs is None else bufs["skip"][i])
+            pool = new(f"{s}_pool", h // 2, w // 2, f, None if bufs is None else bufs["pool"][i])
+            block(f"{s}_block2", F16View.plain(out), h, w, f, skip, pool)
+            skips.append(skip)
+            a = pool
+            h, w = h // 2, w // 2
+        c = fl[-1] * 2
+        a = block("bneck_block1", F16View.plain(a), h, w, c, new("bneck_block1", h, w, c))
+        a = block("bneck_block2", F16View.plain(a), h, w, c, new("bneck_block2", h, w, c))
+        for i in range(len(fl)):
+            stage = len(fl) - i
+            f = fl[stage - 1]
+            s = f"dec{stage}"
+            up = new(f"{s}_upsample", 2 * h, 2 * w, f)
+            ops.f16_conv_transpose2x2(a, n, h, w, c, f, d[f"{s}_upsample/k"], d[f"{s}_upsample/bias"], up)
+            h, w = 2 * h, 2 * w
+            a = block(f"{s}_block1", F16View.concat(up, skips[stage - 1]), h, w, f, new(f"{s}_block1", h, w, f))
+            a = block(f"{s}_block2", F16View.plain(a), h, w, f, new(f"{s}_block2", h, w, f))
+            c = f
+        prob = torch.empty((n, h, w, self.num_classes), dtype=torch.float32, device=self.device)
+        ops.f16_head(a, n, h, w, c, self.num_classes, d["head/k"], d["head/bias"], prob)
+        return prob
+
+    __call__ = forward
+
+    def activation(self, name: str):
+        """The fp16 output of layer `name` from the last forward(x, keep_activations=True)."""
+        if name not in activation_names(self.filters):
+            raise KeyError(f"unknown activation {name!r}")
+        if name not in self._kept:
+            raise RuntimeError("run forward(x, keep_activations=True) first")
+        return self._kept[name]
+
+    def predict(self, x, batch_size: Optional[int] = None, verbose: int = 0):
+        """UNetModel.predict's contract: numpy in -> numpy out, tensor in -> device tensor out."""
+        import torch
+
+        from .metrics import as_device_tensor
+        is_np = not isinstance(x, torch.Tensor)
+        xt = as_device_tensor(x, self.device)
+        bs = batch_size or 32
+        outs = [self.forward(xt[i:i + bs]) for i in range(0, xt.shape[0], bs)]
+        out = torch.cat(outs, 0) if len(outs) > 1 else outs[0]
+        return out.cpu().numpy() if is_np else out

@@ -163,6 +163,13 @@ class UNetModel:
         out = torch.cat(outs, 0) if len(outs) > 1 else outs[0]
         return out.cpu().numpy() if is_np else out
 
+    def freeze(self, dtype: str = "float16"):
+        """A frozen half-precision inference copy (unet_amd.frozen.FrozenUNet): BatchNorm folded
+        into the pointwise weights, fp16 activations and MFMA operands.  It snapshots the weights:
+        later training does not change it.  float16 is the only format."""
+        from .frozen import FrozenUNet
+        return FrozenUNet.from_model(self, dtype)
+
     def _log_values(self, res: torch.Tensor, prefix: str = "") -> Dict[str, float]:
         r = res.detach().cpu().numpy()
         out = {f"{prefix}loss": float(r[0])}

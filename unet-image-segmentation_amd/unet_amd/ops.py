@@ -787,3 +787,110 @@ def adamw_step(param: Tensor, grad: Tensor, m: Tensor, v: Tensor, lr, wd, b1, b2
         _check(t, nm, n)
     _call("unet_adamw_step", (20.0 * n, 28.0 * n), _ptr(param), _ptr(grad), _ptr(m), _ptr(v), n, float(lr), float(wd), float(b1),
            float(b2), float(eps), float(alpha), float(grad_scale), _stream())
+
+
+# ------------------------------------------------- frozen half-precision inference ---
+def _check_dt(t: Tensor, name: str, dtype, numel: Optional[int] = None):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor")
+    if not t.is_cuda:
+        raise ValueError(f"{name}: must be a device (HIP) tensor; there is no CPU path")
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: must be contiguous")
+    if numel is not None and t.numel() != numel:
+        raise ValueError(f"{name}: expected {numel} elements, got {t.numel()}")
+
+
+@dataclass
+class F16View:
+    """Python side of `unet_f16_view`: one fp16 activation, or the zero-copy concat of two."""
+
+    mode: int
+    src0: Tensor
+    c0: int
+    src1: Optional[Tensor] = None
+    c1: int = 0
+
+    @property
+    def channels(self) -> int:
+        return self.c0 + self.c1
+
+    @staticmethod
+    def plain(x: Tensor) -> "F16View":
+        return F16View(L.F16_VIEW_PLAIN, x, x.shape[-1])
+
+    @staticmethod
+    def concat(up: Tensor, skip: Tensor) -> "F16View":
+        return F16View(L.F16_VIEW_CONCAT, up, up.shape[-1], skip, skip.shape[-1])
+
+    def c_struct(self, n: int, h: int, w: int) -> L.UnetF16View:
+        _check_dt(self.src0, "view.src0", torch.float16, n * h * w * self.c0)
+        v = L.UnetF16View()
+        v.mode = self.mode
+        v.c0 = self.c0
+        v.src0 = self.src0.data_ptr()
+        if self.mode == L.F16_VIEW_CONCAT:
+            _check_dt(self.src1, "view.src1", torch.float16, n * h * w * self.c1)
+            v.c1 = self.c1
+            v.src1 = self.src1.data_ptr()
+        return v
+
+
+def f16_image_block(x: Tensor, n: int, h: int, w: int, cin: int, dk: Tensor, cout: int, pw: Tensor, bias: Tensor,
+                    out: Tensor) -> Tensor:
+    """enc1_block1 of the frozen network on the unpadded fp32 image: out fp16 = relu(.)."""
+    _check(x, "x", n * h * w * cin)
+    _check(dk, "depthwise_kernel", 9 * cin)
+    _check(pw, "pw_folded", cin * cout)
+    _check(bias, "bias", cout)
+    _check_dt(out, "out", torch.float16, n * h * w * cout)
+    m = n * h * w
+    _call("unet_f16_image_block", (2.0 * m * cin * (9 + cout), 4.0 * m * cin + 2.0 * m * cout), _ptr(x), n, h, w, cin,
+          _ptr(dk), cout, _ptr(pw), _ptr(bias), _ptr(out), _stream())
+    return out
+
+
+def f16_sepconv(x: F16View, n: int, h: int, w: int, dk: Tensor, cout: int, pw_t: Tensor, bias: Tensor, out: Tensor,
+                out_pool: Optional[Tensor] = None, route: int = 0) -> Tensor:
+    """A folded conv block: out fp16 = relu(fp16(depthwise(x)) . pw_t^T + bias), pw_t fp16 [cout][cin];
+    out_pool (optional) its 2x2 max-pool from the same launch.  route: L.F16_ROUTE_* (tests)."""
+    C = x.channels
+    _check(dk, "depthwise_kernel", 9 * C)
+    _check_dt(pw_t, "pw_t", torch.float16, C * cout)
+    _check(bias, "bias", cout)
+    _check_dt(out, "out", torch.float16, n * h * w * cout)
+    if out_pool is not None:
+        _check_dt(out_pool, "out_pool", torch.float16, n * (h // 2) * (w // 2) * cout)
+    vs = x.c_struct(n, h, w)
+    m = n * h * w
+    nb = 2.0 * m * (C + cout * (1.25 if out_pool is not None else 1.0)) + 2.0 * C * cout + 36.0 * C
+    _call("unet_f16_sepconv", (2.0 * m * C * (9 + cout), nb), ctypes.byref(vs), n, h, w, _ptr(dk), cout, _ptr(pw_t),
+          _ptr(bias), _ptr(out), _ptr(out_pool), int(route), _stream())
+    return out
+
+
+def f16_conv_transpose2x2(x: Tensor, n: int, h: int, w: int, cin: int, cout: int, k: Tensor, bias: Tensor,
+                          out: Tensor) -> Tensor:
+    """Conv2DTranspose(2, strides 2) on fp16: k the Keras (2, 2, cout, cin) kernel as fp16; no activation."""
+    _check_dt(x, "x", torch.float16, n * h * w * cin)
+    _check_dt(k, "kernel", torch.float16, 4 * cout * cin)
+    _check(bias, "bias", cout)
+    _check_dt(out, "out", torch.float16, 4 * n * h * w * cout)
+    m = n * h * w
+    _call("unet_f16_conv_transpose2x2", (8.0 * m * cin * cout, 2.0 * m * (cin + 4 * cout) + 8.0 * cin * cout), _ptr(x),
+          n, h, w, cin, cout, _ptr(k), _ptr(bias), _ptr(out), _stream())
+    return out
+
+
+def f16_head(x: Tensor, n: int, h: int, w: int, cin: int, ncls: int, k: Tensor, bias: Tensor, prob: Tensor) -> Tensor:
+    """Output layer on an fp16 input: fp32 probabilities (sigmoid / softmax)."""
+    _check_dt(x, "x", torch.float16, n * h * w * cin)
+    _check(k, "kernel", cin * ncls)
+    _check(bias, "bias", ncls)
+    _check(prob, "prob", n * h * w * ncls)
+    m = n * h * w
+    _call("unet_f16_head", (2.0 * m * cin * ncls, 2.0 * m * cin + 4.0 * m * ncls), _ptr(x), n, h, w, cin, ncls, _ptr(k),
+          _ptr(bias), _ptr(prob), _stream())
+    return prob
