@@ -196,10 +196,10 @@ def test_convt_bwd_data_bnstats_x3(ops, drop, n, h, w, cin, cout):
 
 
 @pytest.mark.parametrize("m,cin,cout", [(33000, 128, 128), (65536, 256, 512), (4100, 96, 200), (1000, 64, 128)])
-def test_pointwise_bwd_filter_x6(ops, m, cin, cout):
-    """Pointwise weight gradient dW = y^T dz: 128 x 128 output tiles take the split-precision kernel
-    (both operands split as they are staged, 32-pixel stages), 64-wide tiles the fp32 one; within
-    TOL (or 1.5 x the fp32 float32-sum bound) of float64, ragged pixel counts and column tiles."""
+def test_pointwise_bwd_filter_fp32_route(ops, m, cin, cout):
+    """Pointwise weight gradient dW = y^T dz on the fp32-MFMA weight-gradient route, the product
+    library's only one (the split-precision form is a lab variant): 128 x 128 and 64-wide output
+    tiles, ragged pixel counts and column tiles, within TOL of float64."""
     rng = np.random.default_rng(m + cin + cout)
     y = f32(rng.standard_normal((m, cin)))
     dz = f32(rng.standard_normal((m, cout)))
@@ -211,9 +211,10 @@ def test_pointwise_bwd_filter_x6(ops, m, cin, cout):
 
 @pytest.mark.parametrize("drop", [0.0, 0.2])
 @pytest.mark.parametrize("n,h,w,cin,cout", [(4, 32, 32, 256, 128), (2, 33, 17, 96, 40), (16, 16, 16, 512, 256)])
-def test_conv_transpose_bwd_filter_x6(ops, drop, n, h, w, cin, cout):
-    """Conv2DTranspose kernel + bias gradients (the split-precision weight-gradient kernel on its
-    128 x 128 tiles, the bias as the column sums its q-tile-0 blocks take of dU') against float64."""
+def test_conv_transpose_bwd_filter_fp32_route(ops, drop, n, h, w, cin, cout):
+    """Conv2DTranspose kernel + bias gradients on the fp32-MFMA weight-gradient route, the product
+    library's only one (128 x 128 and 64-wide tiles, ragged pixel counts; the bias as the column
+    sums its q-tile-0 blocks take of dU') against float64."""
     rng = np.random.default_rng(n * h * w + cin + cout)
     z = f32(rng.standard_normal((n, h, w, cin)))
     sc, sh = bn_affine(rng, cin)

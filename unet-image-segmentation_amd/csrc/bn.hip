@@ -7,6 +7,7 @@
 // order, and emits the folded affine (scale, shift) that activation views apply on load.
 // Backward is two passes over (da, z): per-channel sums (g, g*xhat) then the elementwise
 // dz, with the ReLU mask and the consumer's dropout mask recomputed, not stored.
+#include "dispatch.h"
 #include "view.h"
 #include "lastblock.h"
 
@@ -711,17 +712,13 @@ int bn_relu_bwd_impl(const float* da, const float* z, int64_t m, int c, const fl
                                                 align_up((size_t)cdiv(p.chunks, kGroupSlabs) * 2 * c * sizeof(double), 256));
     const int ncnt = stats_only ? (int)cdiv(c, 64) : 0;
     dim3 grid(p.ctiles, (unsigned)p.chunks);
-#define UNET_BNB(D, V)                                                                                        \
-    bn_bwd_reduce_kernel<D, V><<<grid, 256, 0, st>>>(da, z, m, c, mu, rs, scale, shift, drop_rate, inv_keep, \
-                                                     drop_seed, p.CT, p.rpc, part, ncnt ? cnt : nullptr, ncnt)
-    if (drop) {
-        if (vec) UNET_BNB(true, true);
-        else UNET_BNB(true, false);
-    } else {
-        if (vec) UNET_BNB(false, true);
-        else UNET_BNB(false, false);
-    }
-#undef UNET_BNB
+    with_bool(drop, [&](auto D) {
+        with_bool(vec, [&](auto V) {
+            bn_bwd_reduce_kernel<D(), V()><<<grid, 256, 0, st>>>(da, z, m, c, mu, rs, scale, shift, drop_rate, inv_keep,
+                                                                 drop_seed, p.CT, p.rpc, part, ncnt ? cnt : nullptr,
+                                                                 ncnt);
+        });
+    });
     UNET_CHECK_LAUNCH("unet_bn_relu_bwd(reduce)");
     if (stats_only)  // statistics-only entry (unet_bn_relu_bwd_stats): reduce + coefficients
         return bwd_stats_finish(part, (int)p.chunks, c, m, use_bn, mean, rstd, dgamma, dbeta, coef_out, scratch, cnt,
@@ -738,17 +735,12 @@ int bn_relu_bwd_impl(const float* da, const float* z, int64_t m, int c, const fl
     UNET_CHECK_LAUNCH("unet_bn_relu_bwd(store)");
     const int64_t work = m * (vec ? c / 4 : c);
     const int g2 = grid_for(work);
-#define UNET_BNA(D, V)                                                                                             \
-    bn_bwd_apply_kernel<D, V><<<g2, 256, 0, st>>>(da, z, m, c, mu, rs, scale, shift, drop_rate, inv_keep, drop_seed, \
-                                                  use_bn, sums, dz)
-    if (drop) {
-        if (vec) UNET_BNA(true, true);
-        else UNET_BNA(true, false);
-    } else {
-        if (vec) UNET_BNA(false, true);
-        else UNET_BNA(false, false);
-    }
-#undef UNET_BNA
+    with_bool(drop, [&](auto D) {
+        with_bool(vec, [&](auto V) {
+            bn_bwd_apply_kernel<D(), V()><<<g2, 256, 0, st>>>(da, z, m, c, mu, rs, scale, shift, drop_rate, inv_keep,
+                                                              drop_seed, use_bn, sums, dz);
+        });
+    });
     UNET_CHECK_LAUNCH("unet_bn_relu_bwd(apply)");
     return 0;
 }

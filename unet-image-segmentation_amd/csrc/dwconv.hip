@@ -7,7 +7,7 @@
 // wave reads/writes contiguous NHWC rows (coalesced 16-B accesses).  The 3x3 halo
 // re-reads hit L1/L2.  The input is read through an activation view (BN+ReLU,
 // max-pool, concat, dropout fused on load).
-#include "view.h"
+#include "dwtile.h"
 
 namespace unet {
 
@@ -325,66 +325,10 @@ int grid_for(int64_t work) {
 
 }  // namespace
 
-// ------------------------------------------------------------ dispatch ----
-#define UNET_DW_DISPATCH(KERNEL, GRID, ...)                                                        \
-    do {                                                                                           \
-        const bool drop_ = x->drop_rate > 0.f;                                                     \
-        switch (x->mode) {                                                                         \
-            case UNET_VIEW_PLAIN:                                                                  \
-                if (drop_) {                                                                       \
-                    if (vec) KERNEL<UNET_VIEW_PLAIN, true, true><<<GRID, kThreads, 0, st>>>(__VA_ARGS__);  \
-                    else KERNEL<UNET_VIEW_PLAIN, true, false><<<GRID, kThreads, 0, st>>>(__VA_ARGS__);     \
-                } else {                                                                           \
-                    if (vec) KERNEL<UNET_VIEW_PLAIN, false, true><<<GRID, kThreads, 0, st>>>(__VA_ARGS__); \
-                    else KERNEL<UNET_VIEW_PLAIN, false, false><<<GRID, kThreads, 0, st>>>(__VA_ARGS__);    \
-                }                                                                                  \
-                break;                                                                             \
-            case UNET_VIEW_BNRELU:                                                                 \
-                if (drop_) {                                                                       \
-                    if (vec) KERNEL<UNET_VIEW_BNRELU, true, true><<<GRID, kThreads, 0, st>>>(__VA_ARGS__);  \
-                    else KERNEL<UNET_VIEW_BNRELU, true, false><<<GRID, kThreads, 0, st>>>(__VA_ARGS__);     \
-                } else {                                                                           \
-                    if (vec) KERNEL<UNET_VIEW_BNRELU, false, true><<<GRID, kThreads, 0, st>>>(__VA_ARGS__); \
-                    else KERNEL<UNET_VIEW_BNRELU, false, false><<<GRID, kThreads, 0, st>>>(__VA_ARGS__);    \
-                }                                                                                  \
-                break;                                                                             \
-            case UNET_VIEW_POOL_BNRELU:                                                            \
-                if (drop_) {                                                                       \
-                    if (vec) KERNEL<UNET_VIEW_POOL_BNRELU, true, true><<<GRID, kThreads, 0, st>>>(__VA_ARGS__);  \
-                    else KERNEL<UNET_VIEW_POOL_BNRELU, true, false><<<GRID, kThreads, 0, st>>>(__VA_ARGS__);     \
-                } else {                                                                           \
-                    if (vec) KERNEL<UNET_VIEW_POOL_BNRELU, false, true><<<GRID, kThreads, 0, st>>>(__VA_ARGS__); \
-                    else KERNEL<UNET_VIEW_POOL_BNRELU, false, false><<<GRID, kThreads, 0, st>>>(__VA_ARGS__);    \
-                }                                                                                  \
-                break;                                                                             \
-            default:                                                                               \
-                if (drop_) {                                                                       \
-                    if (vec) KERNEL<UNET_VIEW_CONCAT, true, true><<<GRID, kThreads, 0, st>>>(__VA_ARGS__);  \
-                    else KERNEL<UNET_VIEW_CONCAT, true, false><<<GRID, kThreads, 0, st>>>(__VA_ARGS__);     \
-                } else {                                                                           \
-                    if (vec) KERNEL<UNET_VIEW_CONCAT, false, true><<<GRID, kThreads, 0, st>>>(__VA_ARGS__); \
-                    else KERNEL<UNET_VIEW_CONCAT, false, false><<<GRID, kThreads, 0, st>>>(__VA_ARGS__);    \
-                }                                                                                  \
-                break;                                                                             \
-        }                                                                                          \
-    } while (0)
-
 static bool view_vec(const unet_view* x) {
     if (x->mode == UNET_VIEW_CONCAT) return x->c0 % 4 == 0 && x->c1 % 4 == 0;
     return x->c0 % 4 == 0;
 }
-
-int dw_tiled_fwd(const DView& v, int mode, bool drop, int N, int H, int W, const float* K, float* Y, hipStream_t st);
-int dw_tiled_bwd_data(const DView& v, int mode, bool drop, int N, int H, int W, const float* K, const float* dY,
-                      float* dx0, float* dx1, hipStream_t st);
-size_t dw_tiled_filter_partials(int N, int H, int W, int C);
-int dw_tiled_bwd_filter(const DView& v, int mode, bool drop, int N, int H, int W, const float* dY, float* part,
-                        int* S_out, hipStream_t st);
-bool dw_tiled_ok(int C);
-int dw_tiled_bwd_data_bnstats(const DView& v, int mode, bool drop, int N, int H, int W, const float* K,
-                              const float* dY, float* dx0, const float* mu, const float* rs, float* bnpart,
-                              hipStream_t st, float* dwpart = nullptr);
-size_t dw_tiled_ntiles(int N, int H, int W, int C);
 
 static int check_dims(const unet_view* x, int n, int h, int w, const char* op) {
     UNET_CHECK_ARG(n > 0 && h > 0 && w > 0, "%s: bad shape n=%d h=%d w=%d", op, n, h, w);
@@ -409,7 +353,11 @@ extern "C" int unet_dwconv3x3_fwd(const unet_view* x, int n, int h, int w, const
     const int64_t work = (int64_t)n * h * w * (vec ? v.C / 4 : v.C);
     hipStream_t st = as_stream(stream);
     const int grid = grid_for(work);
-    UNET_DW_DISPATCH(dw_fwd_kernel, grid, v, n, h, w, dw_kernel, y);
+    with_view(x->mode, x->drop_rate > 0.f, [&](auto M, auto D) {
+        with_bool(vec, [&](auto V) {
+            dw_fwd_kernel<M(), D(), V()><<<grid, kThreads, 0, st>>>(v, n, h, w, dw_kernel, y);
+        });
+    });
     UNET_CHECK_LAUNCH("unet_dwconv3x3_fwd");
     return 0;
 }
@@ -422,7 +370,11 @@ extern "C" int unet_view_materialize(const unet_view* x, int n, int h, int w, fl
     const int64_t work = (int64_t)n * h * w * (vec ? v.C / 4 : v.C);
     hipStream_t st = as_stream(stream);
     const int grid = grid_for(work);
-    UNET_DW_DISPATCH(view_materialize_kernel, grid, v, n, h, w, out);
+    with_view(x->mode, x->drop_rate > 0.f, [&](auto M, auto D) {
+        with_bool(vec, [&](auto V) {
+            view_materialize_kernel<M(), D(), V()><<<grid, kThreads, 0, st>>>(v, n, h, w, out);
+        });
+    });
     UNET_CHECK_LAUNCH("unet_view_materialize");
     return 0;
 }
@@ -440,7 +392,11 @@ extern "C" int unet_dwconv3x3_bwd_data(const unet_view* x, int n, int h, int w, 
     const int64_t work = (int64_t)n * h * w * (vec ? v.C / 4 : v.C);
     hipStream_t st = as_stream(stream);
     const int grid = grid_for(work);
-    UNET_DW_DISPATCH(dw_bwd_data_kernel, grid, v, n, h, w, dw_kernel, dy, dx0, dx1);
+    with_view(x->mode, x->drop_rate > 0.f, [&](auto M, auto D) {
+        with_bool(vec, [&](auto V) {
+            dw_bwd_data_kernel<M(), D(), V()><<<grid, kThreads, 0, st>>>(v, n, h, w, dw_kernel, dy, dx0, dx1);
+        });
+    });
     UNET_CHECK_LAUNCH("unet_dwconv3x3_bwd_data");
     return 0;
 }
@@ -514,7 +470,11 @@ extern "C" int unet_dwconv3x3_bwd_filter(const unet_view* x, int n, int h, int w
     hipStream_t st = as_stream(stream);
     dim3 grid(fp.ctiles, (unsigned)fp.chunks);
     float* part = static_cast<float*>(ws);
-    UNET_DW_DISPATCH(dw_bwd_filter_kernel, grid, v, n, h, w, dy, part, fp.ppc);
+    with_view(x->mode, x->drop_rate > 0.f, [&](auto M, auto D) {
+        with_bool(vec, [&](auto V) {
+            dw_bwd_filter_kernel<M(), D(), V()><<<grid, kThreads, 0, st>>>(v, n, h, w, dy, part, fp.ppc);
+        });
+    });
     UNET_CHECK_LAUNCH("unet_dwconv3x3_bwd_filter");
     return reduce_slabs(part, (int)fp.chunks, (int64_t)9 * v.C, d_dw_kernel, (int64_t)9 * v.C, (int64_t)9 * v.C,
                         st);

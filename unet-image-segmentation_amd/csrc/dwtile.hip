@@ -10,21 +10,9 @@
 // neighbouring tiles hit L2.  The weight gradient uses the same staging and accumulates the 9
 // tap sums in registers over a persistent loop of tiles, then one fixed-order LDS reduction
 // per block -> deterministic per-block partials.
-#include "view.h"
+#include "dwtile.h"
 
 namespace unet {
-
-int dw_tiled_fwd(const DView& v, int mode, bool drop, int N, int H, int W, const float* K, float* Y, hipStream_t st);
-int dw_tiled_bwd_data(const DView& v, int mode, bool drop, int N, int H, int W, const float* K, const float* dY,
-                      float* dx0, float* dx1, hipStream_t st);
-size_t dw_tiled_filter_partials(int N, int H, int W, int C);
-int dw_tiled_bwd_data_bnstats(const DView& v, int mode, bool drop, int N, int H, int W, const float* K,
-                              const float* dY, float* dx0, const float* mu, const float* rs, float* bnpart,
-                              hipStream_t st, float* dwpart = nullptr);
-size_t dw_tiled_ntiles(int N, int H, int W, int C);
-int dw_tiled_bwd_filter(const DView& v, int mode, bool drop, int N, int H, int W, const float* dY, float* part,
-                        int* S_out, hipStream_t st);
-bool dw_tiled_ok(int C);
 
 namespace {
 
@@ -483,53 +471,31 @@ int filter_blocks(const TilePlan& p) {
     return g;
 }
 
-#define UNET_TILE_DISPATCH_QT(KERNEL, MODE, DROP, GRID, ...)                       \
-    switch (p.qt) {                                                                \
-        case 16: KERNEL<MODE, DROP, 16><<<GRID, 256, tile_lds_pad, st>>>(__VA_ARGS__); break; \
-        case 8: KERNEL<MODE, DROP, 8><<<GRID, 256, tile_lds_pad, st>>>(__VA_ARGS__); break;   \
-        case 4: KERNEL<MODE, DROP, 4><<<GRID, 256, tile_lds_pad, st>>>(__VA_ARGS__); break;   \
-        case 2: KERNEL<MODE, DROP, 2><<<GRID, 256, tile_lds_pad, st>>>(__VA_ARGS__); break;   \
-        default: KERNEL<MODE, DROP, 1><<<GRID, 256, tile_lds_pad, st>>>(__VA_ARGS__); break;  \
-    }
-#define UNET_TILE_DISPATCH(KERNEL, GRID, ...)                                                       \
-    switch (mode) {                                                                                 \
-        case UNET_VIEW_PLAIN:                                                                       \
-            if (drop) { UNET_TILE_DISPATCH_QT(KERNEL, UNET_VIEW_PLAIN, true, GRID, __VA_ARGS__) }    \
-            else { UNET_TILE_DISPATCH_QT(KERNEL, UNET_VIEW_PLAIN, false, GRID, __VA_ARGS__) }        \
-            break;                                                                                  \
-        case UNET_VIEW_BNRELU:                                                                      \
-            if (drop) { UNET_TILE_DISPATCH_QT(KERNEL, UNET_VIEW_BNRELU, true, GRID, __VA_ARGS__) }   \
-            else { UNET_TILE_DISPATCH_QT(KERNEL, UNET_VIEW_BNRELU, false, GRID, __VA_ARGS__) }       \
-            break;                                                                                  \
-        case UNET_VIEW_POOL_BNRELU:                                                                 \
-            if (drop) { UNET_TILE_DISPATCH_QT(KERNEL, UNET_VIEW_POOL_BNRELU, true, GRID, __VA_ARGS__) } \
-            else { UNET_TILE_DISPATCH_QT(KERNEL, UNET_VIEW_POOL_BNRELU, false, GRID, __VA_ARGS__) }  \
-            break;                                                                                  \
-        default:                                                                                    \
-            if (drop) { UNET_TILE_DISPATCH_QT(KERNEL, UNET_VIEW_CONCAT, true, GRID, __VA_ARGS__) }   \
-            else { UNET_TILE_DISPATCH_QT(KERNEL, UNET_VIEW_CONCAT, false, GRID, __VA_ARGS__) }       \
-            break;                                                                                  \
-    }
-
 }  // namespace
 
 bool dw_tiled_ok(int C) { return qt_for(C) != 0; }
 
 int dw_tiled_fwd(const DView& v, int mode, bool drop, int N, int H, int W, const float* K, float* Y, hipStream_t st) {
-    const unsigned tile_lds_pad = 0;
     TilePlan p = tile_plan(N, H, W, v.C);
     dim3 grid((unsigned)p.ntiles, (unsigned)p.chunks);
-    UNET_TILE_DISPATCH(dw_tile_fwd, grid, v, N, H, W, p.tiles_w, p.tiles_h, K, Y)
+    with_view(mode, drop, [&](auto M, auto D) {
+        with_int<16, 8, 4, 2, 1>(p.qt, [&](auto Q) {
+            dw_tile_fwd<M(), D(), Q()><<<grid, 256, 0, st>>>(v, N, H, W, p.tiles_w, p.tiles_h, K, Y);
+        });
+    });
     UNET_CHECK_LAUNCH("dwconv3x3_fwd(tiled)");
     return 0;
 }
 
 int dw_tiled_bwd_data(const DView& v, int mode, bool drop, int N, int H, int W, const float* K, const float* dY,
                       float* dx0, float* dx1, hipStream_t st) {
-    const unsigned tile_lds_pad = 0;
     TilePlan p = tile_plan(N, H, W, v.C);
     dim3 grid((unsigned)p.ntiles, (unsigned)p.chunks);
-    UNET_TILE_DISPATCH(dw_tile_bwd_data, grid, v, N, H, W, p.tiles_w, p.tiles_h, K, dY, dx0, dx1)
+    with_view(mode, drop, [&](auto M, auto D) {
+        with_int<16, 8, 4, 2, 1>(p.qt, [&](auto Q) {
+            dw_tile_bwd_data<M(), D(), Q()><<<grid, 256, 0, st>>>(v, N, H, W, p.tiles_w, p.tiles_h, K, dY, dx0, dx1);
+        });
+    });
     UNET_CHECK_LAUNCH("dwconv3x3_bwd_data(tiled)");
     return 0;
 }
@@ -540,44 +506,21 @@ int dw_tiled_bwd_data_bnstats(const DView& v, int mode, bool drop, int N, int H,
     TilePlan p = tile_plan(N, H, W, v.C);
     dim3 grid((unsigned)p.ntiles, (unsigned)p.chunks);
     if (dwpart) {  // (BNRELU view, no dropout: checked by the caller)
-#define UNET_DWF(Q)                                                                                         \
-    dw_tile_bwd_data<UNET_VIEW_BNRELU, false, Q, true, true><<<grid, 256, 0, st>>>(v, N, H, W, p.tiles_w,   \
-                                                                                    p.tiles_h, K, dY, dx0,   \
-                                                                                    nullptr, mu, rs, bnpart, \
-                                                                                    dwpart)
-        switch (p.qt) {
-            case 16: UNET_DWF(16); break;
-            case 8: UNET_DWF(8); break;
-            case 4: UNET_DWF(4); break;
-            case 2: UNET_DWF(2); break;
-            default: UNET_DWF(1); break;
-        }
-#undef UNET_DWF
+        with_int<16, 8, 4, 2, 1>(p.qt, [&](auto Q) {
+            dw_tile_bwd_data<UNET_VIEW_BNRELU, false, Q(), true, true><<<grid, 256, 0, st>>>(
+                v, N, H, W, p.tiles_w, p.tiles_h, K, dY, dx0, nullptr, mu, rs, bnpart, dwpart);
+        });
         UNET_CHECK_LAUNCH("dwconv3x3_bwd_data_bnstats(tiled, filter gradient)");
         return 0;
     }
-#define UNET_BNS(D, Q)                                                                                            \
-    if (mode == UNET_VIEW_POOL_BNRELU)                                                                            \
-        dw_tile_bwd_data<UNET_VIEW_POOL_BNRELU, D, Q, true><<<grid, 256, 0, st>>>(v, N, H, W, p.tiles_w, p.tiles_h, \
-                                                                                  K, dY, dx0, nullptr, mu, rs, bnpart); \
-    else                                                                                                          \
-        dw_tile_bwd_data<UNET_VIEW_BNRELU, D, Q, true><<<grid, 256, 0, st>>>(v, N, H, W, p.tiles_w, p.tiles_h, K,   \
-                                                                             dY, dx0, nullptr, mu, rs, bnpart)
-#define UNET_BNS_QT(D)                      \
-    switch (p.qt) {                          \
-        case 16: UNET_BNS(D, 16); break;     \
-        case 8: UNET_BNS(D, 8); break;       \
-        case 4: UNET_BNS(D, 4); break;       \
-        case 2: UNET_BNS(D, 2); break;       \
-        default: UNET_BNS(D, 1); break;      \
-    }
-    if (drop) {
-        UNET_BNS_QT(true)
-    } else {
-        UNET_BNS_QT(false)
-    }
-#undef UNET_BNS_QT
-#undef UNET_BNS
+    with_int<UNET_VIEW_POOL_BNRELU, UNET_VIEW_BNRELU>(mode, [&](auto M) {
+        with_bool(drop, [&](auto D) {
+            with_int<16, 8, 4, 2, 1>(p.qt, [&](auto Q) {
+                dw_tile_bwd_data<M(), D(), Q(), true><<<grid, 256, 0, st>>>(v, N, H, W, p.tiles_w, p.tiles_h, K, dY,
+                                                                            dx0, nullptr, mu, rs, bnpart);
+            });
+        });
+    });
     UNET_CHECK_LAUNCH("dwconv3x3_bwd_data_bnstats(tiled)");
     return 0;
 }
@@ -591,11 +534,16 @@ size_t dw_tiled_filter_partials(int N, int H, int W, int C) {
 
 int dw_tiled_bwd_filter(const DView& v, int mode, bool drop, int N, int H, int W, const float* dY, float* part,
                         int* S_out, hipStream_t st) {
-    const unsigned tile_lds_pad = (unsigned)lab_knob("UNET_DWF_LDSPAD", 0);  // lab: dynamic LDS pad (fewer blocks per CU)
+    const unsigned lds_pad = (unsigned)lab_knob("UNET_DWF_LDSPAD", 0);  // lab: dynamic LDS pad (fewer blocks per CU)
     TilePlan p = tile_plan(N, H, W, v.C);
     const int G = filter_blocks(p);
     dim3 grid((unsigned)G, (unsigned)p.chunks);
-    UNET_TILE_DISPATCH(dw_tile_bwd_filter, grid, v, N, H, W, p.tiles_w, p.tiles_h, p.ntiles, dY, part)
+    with_view(mode, drop, [&](auto M, auto D) {
+        with_int<16, 8, 4, 2, 1>(p.qt, [&](auto Q) {
+            dw_tile_bwd_filter<M(), D(), Q()><<<grid, 256, lds_pad, st>>>(v, N, H, W, p.tiles_w, p.tiles_h, p.ntiles,
+                                                                          dY, part);
+        });
+    });
     UNET_CHECK_LAUNCH("dwconv3x3_bwd_filter(tiled)");
     *S_out = G;
     return 0;

@@ -11,6 +11,7 @@
 // lane is D[row (i & 3) + 8 (i >> 2) + 4 hh][col r].  GEMM rows are pixels, columns are output
 // channels.
 #include "common.h"
+#include "dispatch.h"
 
 namespace unet {
 namespace {
@@ -418,16 +419,6 @@ __global__ __launch_bounds__(kBlock) void f16_head_kernel(const half_t* __restri
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-template <bool TILE>
-void launch_sep(int nt, dim3 grid, hipStream_t s, const SrcView& v, int n, int h, int w, const float* dw, int cout,
-                const half_t* pw, const float* bias, half_t* out, half_t* pool) {
-    switch (nt) {
-        case 4: f16_sep_kernel<4, TILE><<<grid, kBlock, 0, s>>>(v, n, h, w, dw, cout, pw, bias, out, pool); break;
-        case 2: f16_sep_kernel<2, TILE><<<grid, kBlock, 0, s>>>(v, n, h, w, dw, cout, pw, bias, out, pool); break;
-        default: f16_sep_kernel<1, TILE><<<grid, kBlock, 0, s>>>(v, n, h, w, dw, cout, pw, bias, out, pool); break;
-    }
-}
-
 }  // namespace
 }  // namespace unet
 
@@ -490,10 +481,12 @@ extern "C" int unet_f16_sepconv(const unet_f16_view* x, int n, int h, int w, con
     half_t* o = reinterpret_cast<half_t*>(out);
     half_t* op = reinterpret_cast<half_t*>(out_pool);
     const half_t* pw = reinterpret_cast<const half_t*>(pw_t);
-    if (tile)
-        launch_sep<true>(nt, grid, as_stream(stream), v, n, h, w, dw_kernel, cout, pw, bias, o, op);
-    else
-        launch_sep<false>(nt, grid, as_stream(stream), v, n, h, w, dw_kernel, cout, pw, bias, o, op);
+    hipStream_t s = as_stream(stream);
+    with_int<4, 2, 1>(nt, [&](auto NT) {
+        with_bool(tile, [&](auto TILE) {
+            f16_sep_kernel<NT(), TILE()><<<grid, kBlock, 0, s>>>(v, n, h, w, dw_kernel, cout, pw, bias, o, op);
+        });
+    });
     UNET_CHECK_LAUNCH("unet_f16_sepconv");
     return 0;
 }
@@ -517,12 +510,9 @@ extern "C" int unet_f16_conv_transpose2x2(const unsigned short* x, int n, int h,
     const half_t* ks = reinterpret_cast<const half_t*>(kernel);
     half_t* o = reinterpret_cast<half_t*>(out);
     hipStream_t s = as_stream(stream);
-    if (nt == 4)
-        f16_convt_kernel<4><<<grid, kBlock, 0, s>>>(xs, n, h, w, cin, cout, ks, bias, o);
-    else if (nt == 2)
-        f16_convt_kernel<2><<<grid, kBlock, 0, s>>>(xs, n, h, w, cin, cout, ks, bias, o);
-    else
-        f16_convt_kernel<1><<<grid, kBlock, 0, s>>>(xs, n, h, w, cin, cout, ks, bias, o);
+    with_int<4, 2, 1>(nt, [&](auto NT) {
+        f16_convt_kernel<NT()><<<grid, kBlock, 0, s>>>(xs, n, h, w, cin, cout, ks, bias, o);
+    });
     UNET_CHECK_LAUNCH("unet_f16_conv_transpose2x2");
     return 0;
 }

@@ -18,6 +18,7 @@
 // buffered: the next stage's global loads are in flight while the current stage's MFMAs run.
 // The A operand passes through an activation view (BN+ReLU / dropout / unshuffle) on load.
 #include <cstdlib>
+#include "dispatch.h"
 #include "view.h"
 
 namespace unet {
@@ -1519,25 +1520,20 @@ int launch_rows(const RowsArgs& a0, hipStream_t st, const char* what) {
                 return 0;
             }
         }
-        if (c.bn == 64 && c.bk == 16) launch_rows_tile<64, 16, AMODE, DROP, EPI>(a, st);
-        else if (c.bn == 64 && c.bk == 32) launch_rows_tile<64, 32, AMODE, DROP, EPI>(a, st);
-        else if (c.bn == 128 && c.bk == 32) launch_rows_tile<128, 32, AMODE, DROP, EPI>(a, st);
-        else if (c.bn == 256 && c.bk == 16) launch_rows_tile<256, 16, AMODE, DROP, EPI>(a, st);
-        else launch_rows_tile<128, 16, AMODE, DROP, EPI>(a, st);
+        // the (bn, bk) pairs that have a kernel, as 100 bn + bk; any other pair runs 128 x 16
+        with_int<6416, 6432, 12832, 25616, 12816>(100 * c.bn + c.bk, [&](auto T) {
+            launch_rows_tile<T() / 100, T() % 100, AMODE, DROP, EPI>(a, st);
+        });
         UNET_CHECK_LAUNCH(what);
         return 0;
     }
     if constexpr (AMODE == A_BNBWD || EPI == E_BNPART) {  // vectorised kernel only
         UNET_CHECK_ARG(false, "%s: needs channel counts divisible by 4 and 16-B aligned operands", what);
     } else {
-        const unsigned gm = (unsigned)cdiv(a.M, 128);
-        if (a.N <= 64) {
-            dim3 grid(gm, (unsigned)cdiv(a.N, 64));
-            gemm_rows_kernel<128, 64, AMODE, DROP, EPI><<<grid, 256, 0, st>>>(a);
-        } else {
-            dim3 grid(gm, (unsigned)cdiv(a.N, 128));
-            gemm_rows_kernel<128, 128, AMODE, DROP, EPI><<<grid, 256, 0, st>>>(a);
-        }
+        with_bucket<64, 128>((int)a.N, [&](auto BN) {
+            dim3 grid((unsigned)cdiv(a.M, 128), (unsigned)cdiv(a.N, BN()));
+            gemm_rows_kernel<128, BN(), AMODE, DROP, EPI><<<grid, 256, 0, st>>>(a);
+        });
         UNET_CHECK_LAUNCH(what);
     }
     return 0;
@@ -1577,30 +1573,20 @@ void launch_wgrad_t(const WgradArgs& a, const WgradPlan& w, hipStream_t st) {
     const bool vec = a.P % 4 == 0 && a.Q % 4 == 0 && (AMODE != W_UNSHUFFLE || a.uf % 4 == 0) &&
                      (AMODE == W_UNSHUFFLE || a.a.c0 % 4 == 0) && a.b.c0 % 4 == 0 &&
                      ((uintptr_t)a.a.src0 | (uintptr_t)a.b.src0) % 16 == 0;
-    if (vec || BMODE == W_BNBWD) {
-        if (w.bp == 128 && w.bq == 128 && a.x6 && wgrad_x6()) {
-            gemm_wgrad_vec<128, 128, AMODE, ADROP, BMODE, BDROP, true><<<grid, 256, pad, st>>>(a);
-            return;
-        }
-        if (w.bp == 128 && w.bq == 128)
-            gemm_wgrad_vec<128, 128, AMODE, ADROP, BMODE, BDROP><<<grid, 256, pad, st>>>(a);
-        else if (w.bp == 128)
-            gemm_wgrad_vec<128, 64, AMODE, ADROP, BMODE, BDROP><<<grid, 256, pad, st>>>(a);
-        else if (w.bq == 128)
-            gemm_wgrad_vec<64, 128, AMODE, ADROP, BMODE, BDROP><<<grid, 256, pad, st>>>(a);
-        else
-            gemm_wgrad_vec<64, 64, AMODE, ADROP, BMODE, BDROP><<<grid, 256, pad, st>>>(a);
+    const bool vk = vec || BMODE == W_BNBWD;
+#ifdef UNET_LAB_BUILD  // the split-precision form (wgrad_x6): lab only
+    if (vk && w.bp == 128 && w.bq == 128 && a.x6 && wgrad_x6()) {
+        gemm_wgrad_vec<128, 128, AMODE, ADROP, BMODE, BDROP, true><<<grid, 256, pad, st>>>(a);
         return;
     }
-    if constexpr (BMODE == W_BNBWD) return;  // (unreachable: the vectorised kernel above)
-    else if (w.bp == 128 && w.bq == 128)
-        gemm_wgrad_kernel<128, 128, AMODE, ADROP, BMODE, BDROP><<<grid, 256, pad, st>>>(a);
-    else if (w.bp == 128)
-        gemm_wgrad_kernel<128, 64, AMODE, ADROP, BMODE, BDROP><<<grid, 256, pad, st>>>(a);
-    else if (w.bq == 128)
-        gemm_wgrad_kernel<64, 128, AMODE, ADROP, BMODE, BDROP><<<grid, 256, pad, st>>>(a);
-    else
-        gemm_wgrad_kernel<64, 64, AMODE, ADROP, BMODE, BDROP><<<grid, 256, pad, st>>>(a);
+#endif
+    with_int<128, 64>(w.bp, [&](auto BP) {
+        with_int<128, 64>(w.bq, [&](auto BQ) {
+            if (vk) gemm_wgrad_vec<BP(), BQ(), AMODE, ADROP, BMODE, BDROP><<<grid, 256, pad, st>>>(a);
+            else if constexpr (BMODE != W_BNBWD)  // (W_BNBWD: the vectorised kernel only)
+                gemm_wgrad_kernel<BP(), BQ(), AMODE, ADROP, BMODE, BDROP><<<grid, 256, pad, st>>>(a);
+        });
+    });
 }
 
 // out[P][Q] (row stride ldo) = sum_m A(m, p) B(m, q)
@@ -1615,21 +1601,12 @@ int run_wgrad(WgradArgs a, int amode, int bmode, float* out, void* ws, size_t ws
     const bool ad = a.a.rate > 0.f, bd = a.b.rate > 0.f;
     if (amode == W_PLAIN && bmode == W_PLAIN) {
         launch_wgrad_t<W_PLAIN, false, W_PLAIN, false>(a, w, st);
-    } else if (amode == W_UNSHUFFLE && bmode == W_BNRELU) {
-        if (bd)
-            launch_wgrad_t<W_UNSHUFFLE, false, W_BNRELU, true>(a, w, st);
-        else
-            launch_wgrad_t<W_UNSHUFFLE, false, W_BNRELU, false>(a, w, st);
-    } else if (amode == W_UNSHUFFLE && bmode == W_PLAIN) {
-        if (bd)
-            launch_wgrad_t<W_UNSHUFFLE, false, W_PLAIN, true>(a, w, st);
-        else
-            launch_wgrad_t<W_UNSHUFFLE, false, W_PLAIN, false>(a, w, st);
+    } else if (amode == W_UNSHUFFLE && (bmode == W_BNRELU || bmode == W_PLAIN)) {
+        with_int<W_BNRELU, W_PLAIN>(bmode, [&](auto BM) {
+            with_bool(bd, [&](auto BD) { launch_wgrad_t<W_UNSHUFFLE, false, BM(), BD()>(a, w, st); });
+        });
     } else if (amode == W_BNRELU && bmode == W_PLAIN) {
-        if (ad)
-            launch_wgrad_t<W_BNRELU, true, W_PLAIN, false>(a, w, st);
-        else
-            launch_wgrad_t<W_BNRELU, false, W_PLAIN, false>(a, w, st);
+        with_bool(ad, [&](auto AD) { launch_wgrad_t<W_BNRELU, AD(), W_PLAIN, false>(a, w, st); });
     } else {
         UNET_CHECK_ARG(false, "%s: unsupported wgrad operand modes %d/%d", what, amode, bmode);
     }

@@ -8,6 +8,7 @@
 // dot products (head_fwd_bin_kernel); multi-class: one lane per pixel, the (Cin x ncls) kernel in
 // LDS (broadcast reads).  Dice sums are per (image, class) over H*W: per-block
 // partials, then one fixed-order finalize in double.
+#include "dispatch.h"
 #include "view.h"
 
 namespace unet {
@@ -1052,19 +1053,11 @@ extern "C" int unet_head_fwd(const unet_view* x, int n, int h, int w, int ncls, 
         const int G = x->c0 / 4;
         const int64_t gb = cdiv(M, (int64_t)16 * (64 / G));
         const int grid = (int)(gb > 4096 ? 4096 : gb);
-#define UNET_HB(MODE_)                                                                                       \
-    switch (G) {                                                                                             \
-        case 8: head_fwd_bin_kernel<MODE_, 8><<<grid, 256, 0, st>>>(v, M, kernel, bias, prob); break;         \
-        case 16: head_fwd_bin_kernel<MODE_, 16><<<grid, 256, 0, st>>>(v, M, kernel, bias, prob); break;       \
-        case 32: head_fwd_bin_kernel<MODE_, 32><<<grid, 256, 0, st>>>(v, M, kernel, bias, prob); break;       \
-        default: head_fwd_bin_kernel<MODE_, 64><<<grid, 256, 0, st>>>(v, M, kernel, bias, prob); break;       \
-    }
-        if (x->mode == UNET_VIEW_BNRELU) {
-            UNET_HB(UNET_VIEW_BNRELU)
-        } else {
-            UNET_HB(UNET_VIEW_PLAIN)
-        }
-#undef UNET_HB
+        with_int<UNET_VIEW_BNRELU, UNET_VIEW_PLAIN>(x->mode, [&](auto MODE) {
+            with_int<8, 16, 32, 64>(G, [&](auto GQ) {
+                head_fwd_bin_kernel<MODE(), GQ()><<<grid, 256, 0, st>>>(v, M, kernel, bias, prob);
+            });
+        });
         UNET_CHECK_LAUNCH("unet_head_fwd");
         return 0;
     }
@@ -1072,33 +1065,21 @@ extern "C" int unet_head_fwd(const unet_view* x, int n, int h, int w, int ncls, 
         // multi-class on the matrix cores
         const int grid = (int)(cdiv(M, (int64_t)128) > 2048 ? 2048 : cdiv(M, (int64_t)128));
         const bool vec = (uintptr_t)prob % 16 == 0;
-#define UNET_HFX(MODE_)                                                                                       \
-    switch (x->c0) {                                                                                        \
-        case 16: head_fwdx_kernel<MODE_, 2><<<grid, 256, 0, st>>>(v, M, ncls, kernel, bias, prob, vec); break; \
-        case 32: head_fwdx_kernel<MODE_, 4><<<grid, 256, 0, st>>>(v, M, ncls, kernel, bias, prob, vec); break; \
-        default: head_fwdx_kernel<MODE_, 8><<<grid, 256, 0, st>>>(v, M, ncls, kernel, bias, prob, vec); break; \
-    }
-        if (x->mode == UNET_VIEW_BNRELU) UNET_HFX(UNET_VIEW_BNRELU)
-        else UNET_HFX(UNET_VIEW_PLAIN)
-#undef UNET_HFX
+        with_int<UNET_VIEW_BNRELU, UNET_VIEW_PLAIN>(x->mode, [&](auto MODE) {
+            with_int<16, 32, 64>(x->c0, [&](auto CIN) {
+                head_fwdx_kernel<MODE(), CIN() / 8><<<grid, 256, 0, st>>>(v, M, ncls, kernel, bias, prob, vec);
+            });
+        });
         UNET_CHECK_LAUNCH("unet_head_fwd");
         return 0;
     }
     if (ncls > 1 && x->c0 <= 64 && x->c0 % 4 == 0) {  // multi-class: the register-logit kernel
         const int grid = grid_for(M, 4096);
-#define UNET_HFM(MODE_, NC_) head_fwdm_kernel<MODE_, NC_><<<grid, 256, 0, st>>>(v, M, ncls, kernel, bias, prob)
-#define UNET_HFM_NC(MODE_)                                                                \
-    do {                                                                                  \
-        if (ncls <= 4) UNET_HFM(MODE_, 4);                                                \
-        else if (ncls <= 8) UNET_HFM(MODE_, 8);                                           \
-        else if (ncls <= 16) UNET_HFM(MODE_, 16);                                         \
-        else if (ncls <= 24) UNET_HFM(MODE_, 24);                                         \
-        else UNET_HFM(MODE_, 32);                                                         \
-    } while (0)
-        if (x->mode == UNET_VIEW_BNRELU) UNET_HFM_NC(UNET_VIEW_BNRELU);
-        else UNET_HFM_NC(UNET_VIEW_PLAIN);
-#undef UNET_HFM_NC
-#undef UNET_HFM
+        with_int<UNET_VIEW_BNRELU, UNET_VIEW_PLAIN>(x->mode, [&](auto MODE) {
+            with_bucket<4, 8, 16, 24, 32>(ncls, [&](auto NC) {
+                head_fwdm_kernel<MODE(), NC()><<<grid, 256, 0, st>>>(v, M, ncls, kernel, bias, prob);
+            });
+        });
         UNET_CHECK_LAUNCH("unet_head_fwd");
         return 0;
     }
@@ -1108,17 +1089,11 @@ extern "C" int unet_head_fwd(const unet_view* x, int n, int h, int w, int ncls, 
     const bool multi = ncls > 1;
     const size_t smem = ((size_t)kMaxCin * (multi ? kMaxCls : 1) + (multi ? kMaxCls : 1) +
                          (size_t)TP * (x->c0 + 1)) * sizeof(float);
-    if (x->mode == UNET_VIEW_BNRELU) {
-        if (!multi)
-            head_fwd_kernel<UNET_VIEW_BNRELU, 1><<<grid, 256, smem, st>>>(v, M, ncls, kernel, bias, prob);
-        else
-            head_fwd_kernel<UNET_VIEW_BNRELU, kMaxCls><<<grid, 256, smem, st>>>(v, M, ncls, kernel, bias, prob);
-    } else {
-        if (!multi)
-            head_fwd_kernel<UNET_VIEW_PLAIN, 1><<<grid, 256, smem, st>>>(v, M, ncls, kernel, bias, prob);
-        else
-            head_fwd_kernel<UNET_VIEW_PLAIN, kMaxCls><<<grid, 256, smem, st>>>(v, M, ncls, kernel, bias, prob);
-    }
+    with_int<UNET_VIEW_BNRELU, UNET_VIEW_PLAIN>(x->mode, [&](auto MODE) {
+        with_bool(multi, [&](auto MULTI) {
+            head_fwd_kernel<MODE(), MULTI() ? kMaxCls : 1><<<grid, 256, smem, st>>>(v, M, ncls, kernel, bias, prob);
+        });
+    });
     UNET_CHECK_LAUNCH("unet_head_fwd");
     return 0;
 }
@@ -1247,32 +1222,20 @@ int head_bwd_impl(const unet_view* x, int n, int h, int w, int ncls, const float
         const int grid = head_bwd_grid(M);
         float* part_w = static_cast<float*>(ws);
         float* part_b = part_w + align_up((size_t)grid * x->c0, 64);
-#define UNET_HB1(MODE, L)                                                                                     \
-    head_bwd1_kernel<MODE, L><<<grid, 256, 0, st>>>(v, M, hw, kernel, prob, y_true, sums, smooth, gscale, dx, \
-                                                     part_w, part_b)
-#define UNET_HB1S(L)                                                                                          \
-    head_bwd1_kernel<UNET_VIEW_BNRELU, L, true><<<grid, 256, 0, st>>>(v, M, hw, kernel, prob, y_true, sums,   \
-                                                                      smooth, gscale, dx, part_w, part_b, mu, rs, bnpart)
-#define UNET_HB1D(L)                                                                                          \
-    head_bwd1_kernel<UNET_VIEW_BNRELU, L, true, true><<<grid, 256, 0, st>>>(v, M, hw, kernel, prob, y_true,   \
-                                                                            sums, smooth, gscale, dlogit, part_w, \
-                                                                            part_b, mu, rs, bnpart)
-        if (bnpart && dlogit) {
-            if (loss_kind == UNET_LOSS_DICE) UNET_HB1D(UNET_LOSS_DICE);
-            else UNET_HB1D(UNET_LOSS_IOU);
-        } else if (bnpart) {
-            if (loss_kind == UNET_LOSS_DICE) UNET_HB1S(UNET_LOSS_DICE);
-            else UNET_HB1S(UNET_LOSS_IOU);
-        } else if (x->mode == UNET_VIEW_BNRELU) {
-            if (loss_kind == UNET_LOSS_DICE) UNET_HB1(UNET_VIEW_BNRELU, UNET_LOSS_DICE);
-            else UNET_HB1(UNET_VIEW_BNRELU, UNET_LOSS_IOU);
-        } else {
-            if (loss_kind == UNET_LOSS_DICE) UNET_HB1(UNET_VIEW_PLAIN, UNET_LOSS_DICE);
-            else UNET_HB1(UNET_VIEW_PLAIN, UNET_LOSS_IOU);
-        }
-#undef UNET_HB1
-#undef UNET_HB1S
-#undef UNET_HB1D
+        with_int<UNET_LOSS_DICE, UNET_LOSS_IOU>(loss_kind, [&](auto L) {
+            if (bnpart && dlogit) {
+                head_bwd1_kernel<UNET_VIEW_BNRELU, L(), true, true><<<grid, 256, 0, st>>>(
+                    v, M, hw, kernel, prob, y_true, sums, smooth, gscale, dlogit, part_w, part_b, mu, rs, bnpart);
+            } else if (bnpart) {
+                head_bwd1_kernel<UNET_VIEW_BNRELU, L(), true><<<grid, 256, 0, st>>>(
+                    v, M, hw, kernel, prob, y_true, sums, smooth, gscale, dx, part_w, part_b, mu, rs, bnpart);
+            } else {
+                with_int<UNET_VIEW_BNRELU, UNET_VIEW_PLAIN>(x->mode, [&](auto MODE) {
+                    head_bwd1_kernel<MODE(), L()><<<grid, 256, 0, st>>>(v, M, hw, kernel, prob, y_true, sums, smooth,
+                                                                        gscale, dx, part_w, part_b);
+                });
+            }
+        });
         UNET_CHECK_LAUNCH("unet_head_bwd");
         return reduce_slabs_pair(part_w, x->c0, dkernel, part_b, 1, dbias, grid, st);
     }
@@ -1282,27 +1245,18 @@ int head_bwd_impl(const unet_view* x, int n, int h, int w, int ncls, const float
         float* part_b = part_w + align_up((size_t)grid * x->c0 * ncls, 64);
         const bool vec = ((uintptr_t)prob | (uintptr_t)y_true) % 16 == 0;
         const int ko = lab_knob("UNET_HEAD_KO", 0);  // lab timing knock-outs (0 in the product)
-#define UNET_HMF(MODE_, NC_, L_, S_)                                                                            \
-    head_bwdmf_kernel<MODE_, NC_, L_, S_><<<grid, 256, 0, st>>>(v, M, hw, ncls, kernel, prob, y_true, sums, smooth, \
-                                                              gscale, vec, dx, part_w, part_b, mu, rs, bnpart, ko)
-#define UNET_HMF_NC(MODE_, L_, S_)                   \
-    do {                                             \
-        if (ncls <= 4) UNET_HMF(MODE_, 4, L_, S_);   \
-        else if (ncls <= 8) UNET_HMF(MODE_, 8, L_, S_);  \
-        else if (ncls <= 16) UNET_HMF(MODE_, 16, L_, S_); \
-        else UNET_HMF(MODE_, 24, L_, S_);            \
-    } while (0)
-#define UNET_HMF_L(MODE_, S_)                                            \
-    do {                                                                 \
-        if (loss_kind == UNET_LOSS_DICE) UNET_HMF_NC(MODE_, UNET_LOSS_DICE, S_); \
-        else UNET_HMF_NC(MODE_, UNET_LOSS_IOU, S_);                     \
-    } while (0)
-        if (bnpart) UNET_HMF_L(UNET_VIEW_BNRELU, true);
-        else if (x->mode == UNET_VIEW_BNRELU) UNET_HMF_L(UNET_VIEW_BNRELU, false);
-        else UNET_HMF_L(UNET_VIEW_PLAIN, false);
-#undef UNET_HMF_L
-#undef UNET_HMF_NC
-#undef UNET_HMF
+        auto launch = [&](auto MODE, auto STATS) {
+            with_int<UNET_LOSS_DICE, UNET_LOSS_IOU>(loss_kind, [&](auto L) {
+                with_bucket<4, 8, 16, 24>(ncls, [&](auto NC) {
+                    head_bwdmf_kernel<MODE(), NC(), L(), STATS()><<<grid, 256, 0, st>>>(
+                        v, M, hw, ncls, kernel, prob, y_true, sums, smooth, gscale, vec, dx, part_w, part_b, mu, rs,
+                        bnpart, ko);
+                });
+            });
+        };
+        if (bnpart) launch(Int<UNET_VIEW_BNRELU>{}, std::true_type{});
+        else if (x->mode == UNET_VIEW_BNRELU) launch(Int<UNET_VIEW_BNRELU>{}, std::false_type{});
+        else launch(Int<UNET_VIEW_PLAIN>{}, std::false_type{});
         UNET_CHECK_LAUNCH("unet_head_bwd");
         const int64_t L = (int64_t)x->c0 * ncls;
         return reduce_slabs_pair(part_w, L, dkernel, part_b, ncls, dbias, grid, st);
@@ -1313,34 +1267,20 @@ int head_bwd_impl(const unet_view* x, int n, int h, int w, int ncls, const float
     const size_t ws2_bytes = ws_bytes - dl;
     int64_t g = cdiv(M, 256);
     const int grid = (int)(g > 4096 ? 4096 : g);
-#define UNET_HB(NC, L)                                                                                        \
-    head_bwd_kernel<NC, L><<<grid, 256, 0, st>>>(M, hw, x->c0, ncls, kernel, prob, y_true, sums, smooth, gscale, \
-                                                 dlg, dx)
-    if (ncls > 1 && 256 % CQ == 0) {  // multi-class: kernel in registers, dlogit rows in LDS
-        const int gridm = (int)(cdiv(M, 256) > 2048 ? 2048 : cdiv(M, 256));
-#define UNET_HBM(NC_, L_)                                                                                     \
-    head_bwdm_kernel<NC_, L_><<<gridm, 256, 0, st>>>(M, hw, x->c0, ncls, kernel, prob, y_true, sums, smooth, \
-                                                     gscale, dlg, dx)
-#define UNET_HBM_NC(L_)                                        \
-    do {                                                       \
-        if (ncls <= 4) UNET_HBM(4, L_);                        \
-        else if (ncls <= 8) UNET_HBM(8, L_);                   \
-        else if (ncls <= 16) UNET_HBM(16, L_);                 \
-        else if (ncls <= 24) UNET_HBM(24, L_);                 \
-        else UNET_HBM(32, L_);                                 \
-    } while (0)
-        if (loss_kind == UNET_LOSS_DICE) UNET_HBM_NC(UNET_LOSS_DICE);
-        else UNET_HBM_NC(UNET_LOSS_IOU);
-#undef UNET_HBM_NC
-#undef UNET_HBM
-    } else if (ncls == 1) {
-        if (loss_kind == UNET_LOSS_DICE) UNET_HB(1, UNET_LOSS_DICE);
-        else UNET_HB(1, UNET_LOSS_IOU);
-    } else {
-        if (loss_kind == UNET_LOSS_DICE) UNET_HB(kMaxCls, UNET_LOSS_DICE);
-        else UNET_HB(kMaxCls, UNET_LOSS_IOU);
-    }
-#undef UNET_HB
+    with_int<UNET_LOSS_DICE, UNET_LOSS_IOU>(loss_kind, [&](auto L) {
+        if (ncls > 1 && 256 % CQ == 0) {  // multi-class: kernel in registers, dlogit rows in LDS
+            const int gridm = (int)(cdiv(M, 256) > 2048 ? 2048 : cdiv(M, 256));
+            with_bucket<4, 8, 16, 24, 32>(ncls, [&](auto NC) {
+                head_bwdm_kernel<NC(), L()><<<gridm, 256, 0, st>>>(M, hw, x->c0, ncls, kernel, prob, y_true, sums,
+                                                                   smooth, gscale, dlg, dx);
+            });
+        } else {
+            with_bool(ncls == 1, [&](auto ONE) {
+                head_bwd_kernel<ONE() ? 1 : kMaxCls, L()><<<grid, 256, 0, st>>>(M, hw, x->c0, ncls, kernel, prob,
+                                                                                y_true, sums, smooth, gscale, dlg, dx);
+            });
+        }
+    });
     UNET_CHECK_LAUNCH("unet_head_bwd");
     int rc = head_wgrad(x, M, dlg, ncls, dkernel, ws2, ws2_bytes, st);
     if (rc) return rc;

@@ -1,6 +1,7 @@
 // Shared definitions of the fused SeparableConv2D forward kernels (sepconv.hip: the LDS-A-tile
 // schedule; sepconv_rk.hip: the register-A schedule).  Reference model/u_net.py:14-23.
 #pragma once
+#include "dispatch.h"
 #include "view.h"
 
 namespace unet {

@@ -337,32 +337,24 @@ __global__ __launch_bounds__(128 * WN, sep_min_waves(BN, WN)) void sepconv_fwd_k
     }
 }
 
-template <int MODE, bool DROP, int BN, int WN>
-void launch_tile(const SepArgs& a, bool stats, bool write_y, hipStream_t st) {
-    const dim3 grid((unsigned)(a.N * (a.H / TH) * (a.W / TW)), (unsigned)cdiv(a.Cout, BN));
-    constexpr int NT = 128 * WN;
-    if (stats) {
-        if (write_y) sepconv_fwd_kernel<MODE, DROP, E_STATS, BN, WN, true><<<grid, NT, 0, st>>>(a);
-        else sepconv_fwd_kernel<MODE, DROP, E_STATS, BN, WN, false><<<grid, NT, 0, st>>>(a);
-    } else {
-        if (write_y) sepconv_fwd_kernel<MODE, DROP, E_STORE, BN, WN, true><<<grid, NT, 0, st>>>(a);
-        else sepconv_fwd_kernel<MODE, DROP, E_STORE, BN, WN, false><<<grid, NT, 0, st>>>(a);
-    }
-}
-
-template <int MODE, bool DROP>
-int launch(const SepArgs& a, bool stats, bool write_y, hipStream_t st) {
+int launch(const SepArgs& a, int mode, bool drop, bool stats, bool write_y, hipStream_t st) {
     // the 256-wide, 8-wave tile when it still gives every CU (256) a block; else 128 (measured:
     // tools/bench_sepconv.py, profiles/r1i_sepconv_bn_sweep.log)
     const int64_t mt = (int64_t)a.N * (a.H / TH) * (a.W / TW);
     int bn = a.Cout <= 64 ? 64 : a.Cout <= 128 ? 128 : 256;
     if (bn == 256 && mt * cdiv(a.Cout, 256) < 256) bn = 128;
-    if (bn == 64)
-        launch_tile<MODE, DROP, 64, 2>(a, stats, write_y, st);
-    else if (bn == 128)
-        launch_tile<MODE, DROP, 128, 2>(a, stats, write_y, st);
-    else
-        launch_tile<MODE, DROP, 256, 4>(a, stats, write_y, st);
+    const dim3 grid((unsigned)mt, (unsigned)cdiv(a.Cout, bn));
+    with_view(mode, drop, [&](auto M, auto D) {
+        with_int<64, 128, 256>(bn, [&](auto BN) {
+            constexpr int WN = BN() == 256 ? 4 : 2;  // waves along N
+            with_bool(stats, [&](auto S) {
+                with_bool(write_y, [&](auto WY) {
+                    sepconv_fwd_kernel<M(), D(), S() ? E_STATS : E_STORE, BN(), WN, WY()>
+                        <<<grid, 128 * WN, 0, st>>>(a);
+                });
+            });
+        });
+    });
     UNET_CHECK_LAUNCH("unet_sepconv_fwd");
     return 0;
 }
@@ -484,17 +476,5 @@ extern "C" int unet_sepconv_fwd(const unet_view* x, int n, int h, int w, const f
         return 0;
     }
     UNET_CHECK_ARG(g_sep_schedule != UNET_SEPCONV_RK, "unet_sepconv_fwd: no register-A kernel for this view / shape");
-    switch (x->mode) {
-        case UNET_VIEW_PLAIN:
-            return drop ? launch<UNET_VIEW_PLAIN, true>(a, stats, wy, st) : launch<UNET_VIEW_PLAIN, false>(a, stats, wy, st);
-        case UNET_VIEW_BNRELU:
-            return drop ? launch<UNET_VIEW_BNRELU, true>(a, stats, wy, st)
-                        : launch<UNET_VIEW_BNRELU, false>(a, stats, wy, st);
-        case UNET_VIEW_POOL_BNRELU:
-            return drop ? launch<UNET_VIEW_POOL_BNRELU, true>(a, stats, wy, st)
-                        : launch<UNET_VIEW_POOL_BNRELU, false>(a, stats, wy, st);
-        default:
-            return drop ? launch<UNET_VIEW_CONCAT, true>(a, stats, wy, st)
-                        : launch<UNET_VIEW_CONCAT, false>(a, stats, wy, st);
-    }
+    return launch(a, x->mode, drop, stats, wy, st);
 }

@@ -386,36 +386,6 @@ __global__ __launch_bounds__(256, 2) void sepconv_px_kernel(SepArgs g, int ntile
     }
 }
 
-template <int MODE, bool DROP, int BN, int CIN, int PD>
-void launch_px_t(const SepArgs& a, bool stats, bool write_y, int ntiles, int grid, hipStream_t st) {
-#define UNET_PX(ST, WY) sepconv_px_kernel<MODE, DROP, ST, BN, CIN, WY, PD><<<grid, 256, 0, st>>>(a, ntiles)
-    if (stats) { if (write_y) UNET_PX(true, true); else UNET_PX(true, false); }
-    else { if (write_y) UNET_PX(false, true); else UNET_PX(false, false); }
-#undef UNET_PX
-}
-
-template <int MODE, bool DROP, int PD>
-void launch_px_p(const SepArgs& a, bool stats, bool write_y, int ntiles, int grid, hipStream_t st) {
-    if (a.Cout == 64) {
-        if (a.Cin == 64) { launch_px_t<MODE, DROP, 64, 64, PD>(a, stats, write_y, ntiles, grid, st); return; }
-        launch_px_t<MODE, DROP, 64, 128, PD>(a, stats, write_y, ntiles, grid, st);
-    } else {
-        if (a.Cin == 64) launch_px_t<MODE, DROP, 128, 64, PD>(a, stats, write_y, ntiles, grid, st);
-        else launch_px_t<MODE, DROP, 128, 128, PD>(a, stats, write_y, ntiles, grid, st);
-    }
-}
-
-template <int MODE, bool DROP>
-void launch_px_m(const SepArgs& a, bool stats, bool write_y, int pd, int ntiles, int grid, hipStream_t st) {
-#ifdef UNET_LAB_BUILD  // other prefetch depths: lab only (UNET_PX_PD=1, 3, 4)
-    if (pd == 1) { launch_px_p<MODE, DROP, 1>(a, stats, write_y, ntiles, grid, st); return; }
-    if (pd == 3) { launch_px_p<MODE, DROP, 3>(a, stats, write_y, ntiles, grid, st); return; }
-    if (pd == 4) { launch_px_p<MODE, DROP, 4>(a, stats, write_y, ntiles, grid, st); return; }
-#endif
-    (void)pd;
-    launch_px_p<MODE, DROP, 2>(a, stats, write_y, ntiles, grid, st);
-}
-
 }  // namespace
 
 bool px_supported(const SepArgs& a, int mode, bool all_shapes) {
@@ -441,12 +411,28 @@ int launch_px(const SepArgs& a, int mode, bool drop, bool stats, bool write_y, h
     const int per = (ntiles + slots - 1) / slots;
     const int grid = (ntiles + per - 1) / per;
     const int pd = lab_knob("UNET_PX_PD", 2);
-#define UNET_PXM(M) \
-    (drop ? launch_px_m<M, true>(a, stats, write_y, pd, ntiles, grid, st) : launch_px_m<M, false>(a, stats, write_y, pd, ntiles, grid, st))
-    if (mode == UNET_VIEW_PLAIN) UNET_PXM(UNET_VIEW_PLAIN);
-    else if (mode == UNET_VIEW_BNRELU) UNET_PXM(UNET_VIEW_BNRELU);
-    else UNET_PXM(UNET_VIEW_CONCAT);
-#undef UNET_PXM
+    auto launch = [&](auto PD) {  // PD: the prefetch depth
+        with_int<UNET_VIEW_PLAIN, UNET_VIEW_BNRELU, UNET_VIEW_CONCAT>(mode, [&](auto M) {
+            with_bool(drop, [&](auto D) {
+                with_int<64, 128>(a.Cout, [&](auto BN) {
+                    with_int<64, 128>(a.Cin, [&](auto CIN) {
+                        with_bool(stats, [&](auto S) {
+                            with_bool(write_y, [&](auto WY) {
+                                sepconv_px_kernel<M(), D(), S(), BN(), CIN(), WY(), PD()>
+                                    <<<grid, 256, 0, st>>>(a, ntiles);
+                            });
+                        });
+                    });
+                });
+            });
+        });
+    };
+#ifdef UNET_LAB_BUILD  // other prefetch depths: lab only (UNET_PX_PD=1, 3, 4)
+    with_int<1, 3, 4, 2>(pd, launch);
+#else
+    (void)pd;
+    launch(Int<2>{});
+#endif
     return 0;
 }
 

@@ -491,34 +491,6 @@ __global__ __launch_bounds__(256, X6 && BN <= 128 ? 3 : 2) void sepconv_rk_kerne
     }
 }
 
-template <int MODE, bool DROP, int BN, bool X6>
-void launch_rk_x(const SepArgs& a, bool stats, bool write_y, hipStream_t st) {
-    const dim3 grid((unsigned)(a.N * (a.H / TH) * (a.W / TW)), (unsigned)cdiv(a.Cout, BN));
-    if (stats) {
-        if (write_y) sepconv_rk_kernel<MODE, DROP, E_STATS, BN, true, X6><<<grid, 256, 0, st>>>(a);
-        else sepconv_rk_kernel<MODE, DROP, E_STATS, BN, false, X6><<<grid, 256, 0, st>>>(a);
-    } else {
-        if (write_y) sepconv_rk_kernel<MODE, DROP, E_STORE, BN, true, X6><<<grid, 256, 0, st>>>(a);
-        else sepconv_rk_kernel<MODE, DROP, E_STORE, BN, false, X6><<<grid, 256, 0, st>>>(a);
-    }
-}
-
-template <int MODE, bool DROP, int BN>
-void launch_rk_x6(const SepArgs& a, bool stats, bool write_y, hipStream_t st) {
-    if constexpr (MODE != UNET_VIEW_POOL_BNRELU) launch_rk_x<MODE, DROP, BN, true>(a, stats, write_y, st);
-}
-
-template <int MODE, bool DROP, int BN>
-void launch_rk_t(const SepArgs& a, bool stats, bool write_y, hipStream_t st) {
-    if constexpr (MODE != UNET_VIEW_POOL_BNRELU) {
-        if (a.pkx && rk_x6_supported(MODE, a.Cin)) {
-            launch_rk_x<MODE, DROP, BN, true>(a, stats, write_y, st);
-            return;
-        }
-    }
-    launch_rk_x<MODE, DROP, BN, false>(a, stats, write_y, st);
-}
-
 }  // namespace
 
 bool rk_x6_supported(int mode, int cin) { return mode != UNET_VIEW_POOL_BNRELU && cin % 16 == 0 && cin >= 64; }
@@ -538,21 +510,22 @@ int launch_rk(const SepArgs& a, int mode, bool drop, bool stats, bool write_y, h
     // and the 64 x 64 level's 512 pixel tiles fill the 512 block slots in one round
     const bool x6 = a.pkx && rk_x6_supported(mode, a.Cin);
     const int bn = a.Cout <= 64 ? 64 : (x6 && a.Cout >= 256 ? 256 : 128);
-#define UNET_RK(M, D)                                                          \
-    do {                                                                       \
-        if (bn == 64) launch_rk_t<M, D, 64>(a, stats, write_y, st);            \
-        else if (bn == 128) launch_rk_t<M, D, 128>(a, stats, write_y, st);     \
-        else launch_rk_x6<M, D, 256>(a, stats, write_y, st);                   \
-    } while (0)
-    switch (mode) {
-        case UNET_VIEW_PLAIN: if (drop) UNET_RK(UNET_VIEW_PLAIN, true); else UNET_RK(UNET_VIEW_PLAIN, false); break;
-        case UNET_VIEW_BNRELU: if (drop) UNET_RK(UNET_VIEW_BNRELU, true); else UNET_RK(UNET_VIEW_BNRELU, false); break;
-        case UNET_VIEW_POOL_BNRELU:
-            if (drop) UNET_RK(UNET_VIEW_POOL_BNRELU, true); else UNET_RK(UNET_VIEW_POOL_BNRELU, false);
-            break;
-        default: if (drop) UNET_RK(UNET_VIEW_CONCAT, true); else UNET_RK(UNET_VIEW_CONCAT, false); break;
-    }
-#undef UNET_RK
+    const dim3 grid((unsigned)(a.N * (a.H / TH) * (a.W / TW)), (unsigned)cdiv(a.Cout, bn));
+    with_view(mode, drop, [&](auto M, auto D) {
+        with_int<64, 128, 256>(bn, [&](auto BN) {
+            with_bool(x6, [&](auto X6) {
+                // no split-precision kernel for the max-pool view, and the 256-column tile only with it
+                if constexpr (X6() ? M() != UNET_VIEW_POOL_BNRELU : BN() != 256) {
+                    with_bool(stats, [&](auto S) {
+                        with_bool(write_y, [&](auto WY) {
+                            sepconv_rk_kernel<M(), D(), S() ? E_STATS : E_STORE, BN(), WY(), X6()>
+                                <<<grid, 256, 0, st>>>(a);
+                        });
+                    });
+                }
+            });
+        });
+    });
     return 0;
 }
 

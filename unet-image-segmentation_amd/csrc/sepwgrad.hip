@@ -14,6 +14,7 @@
 // Both run 4-wave blocks over 4 x 16 pixel tiles, two blocks per CU; each block walks a run of
 // tiles, one fixed-order slab per block, reduced by reduce_slabs in fixed order.
 #include "common.h"
+#include "dispatch.h"
 #include "view.h"
 
 namespace unet {
@@ -492,14 +493,6 @@ SwPlan sw_plan(int n, int h, int w, int cin) {
     return p;
 }
 
-template <int MODE, bool DROP>
-void launch_sw(const SwArgs& a, int cout, int blocks, hipStream_t st) {
-    if (a.da_dl) sepconv_bwd_fused_kernel<MODE, true><<<blocks, fb::NT, 0, st>>>(a);
-    else if (a.da) sepconv_bwd_fused_kernel<MODE><<<blocks, fb::NT, 0, st>>>(a);
-    else if (cout == 128) sepconv_bwd_filter2_kernel<MODE, DROP, 128><<<blocks, fb::NT, 0, st>>>(a);
-    else sepconv_bwd_filter2_kernel<MODE, DROP, 64><<<blocks, fb::NT, 0, st>>>(a);
-}
-
 }  // namespace
 }  // namespace unet
 
@@ -546,20 +539,19 @@ int run_sw(const unet_view* x, int n, int h, int w, const float* dw_kernel, SwAr
     const int blocks = p.S * p.ncig;
     hipStream_t st = as_stream(stream);
     const bool drop = x->drop_rate > 0.f;
-    switch (x->mode) {
-        case UNET_VIEW_PLAIN:
-            if (drop) launch_sw<UNET_VIEW_PLAIN, true>(a, cout, blocks, st);
-            else launch_sw<UNET_VIEW_PLAIN, false>(a, cout, blocks, st);
-            break;
-        case UNET_VIEW_BNRELU:
-            if (drop) launch_sw<UNET_VIEW_BNRELU, true>(a, cout, blocks, st);
-            else launch_sw<UNET_VIEW_BNRELU, false>(a, cout, blocks, st);
-            break;
-        default:
-            if (drop) launch_sw<UNET_VIEW_CONCAT, true>(a, cout, blocks, st);
-            else launch_sw<UNET_VIEW_CONCAT, false>(a, cout, blocks, st);
-            break;
-    }
+    with_int<UNET_VIEW_PLAIN, UNET_VIEW_BNRELU, UNET_VIEW_CONCAT>(x->mode, [&](auto M) {
+        if (a.da_dl) {
+            sepconv_bwd_fused_kernel<M(), true><<<blocks, fb::NT, 0, st>>>(a);
+        } else if (a.da) {
+            sepconv_bwd_fused_kernel<M()><<<blocks, fb::NT, 0, st>>>(a);
+        } else {
+            with_bool(drop, [&](auto D) {
+                with_int<128, 64>(cout, [&](auto CO) {
+                    sepconv_bwd_filter2_kernel<M(), D(), CO()><<<blocks, fb::NT, 0, st>>>(a);
+                });
+            });
+        }
+    });
     UNET_CHECK_LAUNCH(op);
     const int64_t lp = (int64_t)cin * cout, ld = (int64_t)9 * cin;
     return reduce_slabs_pair(a.pw_slab, lp, d_pw_kernel, a.dw_slab, ld, d_dw_kernel, p.S, st);
