@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UNET_ABI_VERSION 13
+#define UNET_ABI_VERSION 14
 
 typedef void* unet_stream_t; /* hipStream_t */
 
@@ -576,6 +576,75 @@ int unet_f16_conv_transpose2x2(const unsigned short* x, int n, int h, int w, int
  * (1, 1, cin, ncls) and bias, fp32 prob (n, h, w, ncls) = sigmoid (ncls == 1) or softmax.      */
 int unet_f16_head(const unsigned short* x, int n, int h, int w, int cin, int ncls,
                   const float* kernel, const float* bias, float* prob, unet_stream_t stream);
+
+/* ----- Frozen int8 inference (ABI 14) --------------------------------------------------------
+ * The reference converter's next mode (int8 with a representative dataset): the folded network
+ * with one-byte activations and v_mfma_i32_32x32x32_i8 products.  Scales come from a calibration
+ * run (unet_amd/frozen.py: collect_ranges, quantize_weights).  THE ARITHMETIC CONTRACT, which the
+ * kernels and the test emulator (tests/i8_emulation.py) both implement exactly:
+ *
+ * Storage.  NHWC bytes, dense, 16-byte aligned.  Post-ReLU activations (every conv block's output
+ * and its max-pool) are uint8, x = s q, q in [0, 255]; upsample outputs (signed) are int8, q in
+ * [-127, 127].  Spatial padding is q = 0 in both types.  Scales: s = max|.| / 255 (uint8) or / 127
+ * (int8) over the calibration set, s = 1 where the maximum is 0.
+ *
+ * Conv block.  taps[t][c] = dw[t][c] s_in[c] / s_y in fp32 (host; s_in is per input channel, so a
+ * concat of an int8 half and a uint8 half with different scales needs no rescaling pass).
+ *   a = 0; for t = 0..8: a = fmaf((float)x_q[t][c], taps[t][c], a)
+ *   y_q = clamp(rintf(a), -127, 127) as int8                          (the A operand)
+ *   B = the folded pointwise kernel as int8, per-output-channel scale s_w[co] = max|pw'[:, co]| / 127
+ *       (1 where the column is all zero); acc is int32, exact
+ *   v = fmaf((float)acc, mult[co], bias_q[co]);  q_out = clamp(rintf(v), 0, 255)
+ * with mult = s_y s_w[co] / s_out and bias_q = bias[co] / s_out computed in float64 on the host and
+ * rounded to fp32.  The clamp is the ReLU; the max-pool is the max of the four q_out.
+ *
+ * Upsample (Conv2DTranspose 2x2).  A = the uint8 input XOR 0x80 (q - 128 as int8); B = the kernel as
+ * int8 with one scale per column (a, b, co); colsum[col] = sum_k B[col][k] in int32 (host).
+ *   acc32 = acc + 128 colsum[col]  (int32);  v = fmaf((float)acc32, mult[col], bias_q[co])
+ *   q = clamp(rintf(v), -127, 127)
+ * (float)acc32 is the int32 -> fp32 conversion, round to nearest even: at cin = 1024 |acc32| can
+ * exceed 2^24, which is allowed and part of the contract.
+ *
+ * Image block (enc1_block1).  fp32 input and arithmetic as unet_f16_image_block;
+ * q = clamp(rintf(relu(z) / s_out), 0, 255).
+ * Head.  Reads uint8; fp32 kernel with the input scale folded in on the host; fp32 probabilities. */
+enum { UNET_I8_VIEW_PLAIN = 0, /* x = src0 (n, h, w, c0)                     */
+       UNET_I8_VIEW_CONCAT = 1 /* x = [src0 (c0) | src1 (c1)] (u_net.py:95-96) */ };
+typedef struct unet_i8_view {
+    int32_t mode;
+    int32_t c0;          /* CONCAT: a multiple of 16; c0 + c1 is a multiple of 32 */
+    int32_t c1;          /* CONCAT only, else 0 */
+    int32_t signed0;     /* src0 holds int8 (nonzero) or uint8 (0) */
+    int32_t signed1;     /* the same for src1 */
+    int32_t reserved0;
+    const void* src0;
+    const void* src1;
+} unet_i8_view;
+
+/* The image block on the caller's unpadded fp32 image (n, h, w, cin <= 4): out (n, h, w, cout)
+ * uint8 with scale out_scale.  dw_kernel (3, 3, cin, 1), pw_folded (cin, cout), bias fp32;
+ * cout % 32 == 0.                                                                             */
+int unet_i8_image_block(const float* x, int n, int h, int w, int cin, const float* dw_kernel,
+                        int cout, const float* pw_folded, const float* bias, float out_scale,
+                        unsigned char* out, unet_stream_t stream);
+/* A quantised conv_block: taps fp32 [9][C], C = c0 + c1; pw_q int8 [cout][C] (k contiguous); mult and
+ * bias_q fp32 [cout]; out (n, h, w, cout) uint8; out_pool (optional, h and w even) its 2x2 max from
+ * the same launch.  C and cout must be multiples of 32 and a concat's c0 a multiple of 16; anything
+ * else is refused.  route as unet_f16_sepconv (0 auto, 1 rows, 2 tile; bitwise the same result). */
+int unet_i8_sepconv(const unet_i8_view* x, int n, int h, int w, const float* taps, int cout,
+                    const signed char* pw_q, const float* mult, const float* bias_q,
+                    unsigned char* out, unsigned char* out_pool, int route, unet_stream_t stream);
+/* Conv2DTranspose(f, 2, strides=2) on a uint8 input (n, h, w, cin): kernel_q int8 in the Keras
+ * (2, 2, cout, cin) layout, colsum int32 and mult fp32 per column [4 cout], bias_q fp32 [cout];
+ * out (n, 2h, 2w, cout) int8.  cin and cout multiples of 32.                                   */
+int unet_i8_conv_transpose2x2(const unsigned char* x, int n, int h, int w, int cin, int cout,
+                              const signed char* kernel_q, const int32_t* colsum,
+                              const float* mult, const float* bias_q, signed char* out,
+                              unet_stream_t stream);
+/* Output layer on a uint8 input (n, h, w, cin), cin % 8 == 0: fp32 kernel (1, 1, cin, ncls) with the
+ * input scale folded in, fp32 bias, fp32 prob = sigmoid (ncls == 1) or softmax.                */
+int unet_i8_head(const unsigned char* x, int n, int h, int w, int cin, int ncls,
+                 const float* kernel, const float* bias, float* prob, unet_stream_t stream);
 
 #ifdef __cplusplus
 }

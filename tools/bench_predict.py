@@ -1,10 +1,14 @@
 """Inference latency, eager vs the captured HIP graph (UNetEngine.graph_predict): ms per predict()
 call at 256x256x3 (configs[1]'s network) for a few batch sizes, device-resident input, median of
-timed calls after warm-up.  Usage: python tools/bench_predict.py [--frozen] [sizes...]
+timed calls after warm-up.  Usage: python tools/bench_predict.py [--frozen] [--int8] [sizes...]
 
 --frozen also times the frozen fp16 network (UNetModel.freeze()): per batch size the three
 variants alternate round by round in one process on the same device-resident input, and the JSON
-line gains frozen_ms and frozen_speedup_vs_graph."""
+line gains frozen_ms and frozen_speedup_vs_graph.
+
+--int8 (beside --frozen) adds the frozen int8 network (UNetModel.freeze(dtype="int8"), calibrated
+on 8 random images) as a fourth variant in the same alternation; the line gains int8_ms,
+int8_over_f16 (int8_ms / frozen_ms, < 1 is faster) and int8_max_abs_diff against the graph."""
 import json
 import os
 import sys
@@ -48,11 +52,16 @@ def timed_alternating(fns, reps=50):
 def main():
     args = sys.argv[1:]
     frozen = "--frozen" in args
-    batches = [int(a) for a in args if a != "--frozen"] or [1, 4, 16]
+    int8 = "--int8" in args
+    if int8 and not frozen:
+        sys.exit("--int8 is timed beside --frozen: pass both")
+    batches = [int(a) for a in args if a not in ("--frozen", "--int8")] or [1, 4, 16]
     model = UNetModel((256, 256, 3), 1, dropout_rate=0.2, device="cuda:0")
     eng = model.engine
     fz = model.freeze() if frozen else None
     rng = np.random.default_rng(5)
+    fq = model.freeze(dtype="int8", calibration=rng.random((8, 256, 256, 3), dtype=np.float32),
+                      batch_size=4) if int8 else None
 
     def eager(x):
         eng.graph_predict = False
@@ -64,7 +73,10 @@ def main():
 
     for n in batches:
         x = torch.as_tensor(rng.random((n, 256, 256, 3), dtype=np.float32), device="cuda:0")
-        if frozen:
+        if int8:
+            t_e, t_g, t_f, t_q = timed_alternating([lambda: eager(x), lambda: graph(x), lambda: fz.predict(x),
+                                                    lambda: fq.predict(x)])
+        elif frozen:
             t_e, t_g, t_f = timed_alternating([lambda: eager(x), lambda: graph(x), lambda: fz.predict(x)])
         else:
             t_e = timed(lambda: eager(x))
@@ -78,6 +90,10 @@ def main():
             rec.update(frozen_ms=round(t_f, 3), frozen_speedup_vs_graph=round(t_g / t_f, 3),
                        img_per_s_frozen=round(n / t_f * 1e3, 1),
                        frozen_max_abs_diff=float((fz.predict(x) - g).abs().max()))
+        if int8:
+            rec.update(int8_ms=round(t_q, 3), int8_over_f16=round(t_q / t_f, 3),
+                       img_per_s_int8=round(n / t_q * 1e3, 1),
+                       int8_max_abs_diff=float((fq.predict(x) - g).abs().max()))
         print(json.dumps(rec), flush=True)
 
 

@@ -112,7 +112,7 @@ def main(argv=None):
         from unet_amd.frozen import FrozenUNet, is_frozen_file
         if is_frozen_file(args.model):  # an artefact of scripts/convert_to_frozen.py
             model = FrozenUNet.load(args.model)
-            print("Frozen float16 model loaded successfully.")
+            print(f"Frozen {model.dtype} model loaded successfully.")
         else:
             from model.u_net import U_NET
             model = U_NET((IMG_HEIGHT, IMG_WIDTH, 3), 1)

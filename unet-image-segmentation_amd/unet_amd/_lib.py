@@ -12,12 +12,14 @@ from pathlib import Path
 
 LIB_NAME = "libunet_hip.so"
 LIB_PATH = Path(os.environ.get("UNET_HIP_LIB", Path(__file__).with_name(LIB_NAME)))
-ABI_VERSION = 13
+ABI_VERSION = 14
 SPLIT_MAX_SEGS = 64  # UNET_SPLIT_MAX_SEGS
 
 VIEW_PLAIN, VIEW_BNRELU, VIEW_POOL_BNRELU, VIEW_CONCAT = 0, 1, 2, 3
 F16_VIEW_PLAIN, F16_VIEW_CONCAT = 0, 1
 F16_ROUTE_AUTO, F16_ROUTE_ROWS, F16_ROUTE_TILE = 0, 1, 2
+I8_VIEW_PLAIN, I8_VIEW_CONCAT = 0, 1
+I8_ROUTE_AUTO, I8_ROUTE_ROWS, I8_ROUTE_TILE = 0, 1, 2
 LOSS_DICE, LOSS_IOU = 0, 1
 
 
@@ -54,8 +56,24 @@ class UnetF16View(ctypes.Structure):
     ]
 
 
+class UnetI8View(ctypes.Structure):
+    """Mirror of `unet_i8_view` (include/unet_hip.h)."""
+
+    _fields_ = [
+        ("mode", c_int32),
+        ("c0", c_int32),
+        ("c1", c_int32),
+        ("signed0", c_int32),
+        ("signed1", c_int32),
+        ("reserved0", c_int32),
+        ("src0", c_void_p),
+        ("src1", c_void_p),
+    ]
+
+
 _VP = POINTER(UnetView)
 _HVP = POINTER(UnetF16View)
+_QVP = POINTER(UnetI8View)
 P = c_void_p
 # name -> (restype, argtypes); exactly the entry points of include/unet_hip.h
 SIGNATURES = {
@@ -138,6 +156,10 @@ SIGNATURES = {
     "unet_f16_sepconv": (c_int, [_HVP, c_int, c_int, c_int, P, c_int, P, P, P, P, c_int, P]),
     "unet_f16_conv_transpose2x2": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
     "unet_f16_head": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "unet_i8_image_block": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, P, P, c_float, P, P]),
+    "unet_i8_sepconv": (c_int, [_QVP, c_int, c_int, c_int, P, c_int, P, P, P, P, P, c_int, P]),
+    "unet_i8_conv_transpose2x2": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P]),
+    "unet_i8_head": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
 }
 
 _lib = None

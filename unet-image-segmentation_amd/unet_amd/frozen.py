@@ -1,5 +1,6 @@
-"""Frozen half-precision inference: the engine's counterpart of the reference's deployment step
-(scripts/tensorflow_lite/convert_to_tflite.py --float16).
+"""Frozen inference: the engine's counterpart of the reference's deployment step
+(scripts/tensorflow_lite/convert_to_tflite.py --float16, and the int8 mode with a representative
+dataset that the converter names next).
 
 `fold_weights` is pure NumPy (float64): BatchNormalization (model/u_net.py:22-23, eps 1e-3) folds
 into the pointwise kernel and a bias, and the matrix-core operands are rounded to fp16.
@@ -10,6 +11,10 @@ pointwise GEMMs are one fp16 MFMA product per step with fp32 accumulation.
 Rounding to fp16 (nearest even) happens at exactly four places: the folded pointwise / upsample
 kernels (here), each block's depthwise output, each block's output after bias + ReLU, each
 upsample's output after bias.  Everything else is fp32.
+
+The int8 format (`quantize_weights`, `collect_ranges`, `FrozenUNetI8`, csrc/frozen_i8.hip) stores
+activations as one byte with per-tensor scales from a calibration run and multiplies on the int8
+MFMA; its arithmetic contract is written out in include/unet_hip.h ("Frozen int8 inference").
 """
 from __future__ import annotations
 
@@ -19,7 +24,9 @@ import numpy as np
 
 BN_EPS = 1e-3  # keras.layers.BatchNormalization default
 F16_MAX = 65504.0
-FORMAT_VERSION = 1
+FORMAT_VERSION = 1       # float16 archives
+FORMAT_VERSION_INT8 = 2  # int8 archives
+_FORMATS = {"float16": FORMAT_VERSION, "int8": FORMAT_VERSION_INT8}
 MARKER = "__frozen_unet__"
 IMAGE_BLOCK = "enc1_block1"
 
@@ -105,13 +112,18 @@ def fold_weights(weights: Dict[str, np.ndarray], num_classes: int, use_batch_nor
 
 
 # ---------------------------------------------------------------------- the artefact ---
-def to_archive(folded: Dict[str, np.ndarray], input_size, num_classes: int, filters) -> Dict[str, np.ndarray]:
+def to_archive(folded: Dict[str, np.ndarray], input_size, num_classes: int, filters,
+               dtype: str = "float16") -> Dict[str, np.ndarray]:
     """The arrays of a frozen .npz: the folded variables in Keras layouts (':' for '/'), the
-    geometry, the dtype, a format version and the marker key."""
-    arc = {k.replace("/", ":"): np.ascontiguousarray(v) for k, v in folded.items()}
+    geometry, the dtype, a format version (1 for float16, 2 for int8: the arrays are then those of
+    quantize_weights) and the marker key."""
+    if dtype not in _FORMATS:
+        raise ValueError(f"frozen dtype {dtype!r}: float16 and int8 exist")
+    arc = {k.replace("/", ":"): np.ascontiguousarray(v) if np.ndim(v) else np.asarray(v)  # (0-d: the int8 scales)
+           for k, v in folded.items()}
     arc[MARKER] = np.asarray(1, np.int32)
-    arc["format_version"] = np.asarray(FORMAT_VERSION, np.int32)
-    arc["dtype"] = np.asarray("float16")
+    arc["format_version"] = np.asarray(_FORMATS[dtype], np.int32)
+    arc["dtype"] = np.asarray(dtype)
     arc["input_size"] = np.asarray(tuple(int(v) for v in input_size), np.int32)
     arc["num_classes"] = np.asarray(int(num_classes), np.int32)
     arc["filters"] = np.asarray(tuple(int(f) for f in filters), np.int32)
@@ -127,11 +139,12 @@ def from_archive(arc) -> Tuple[Dict[str, np.ndarray], dict]:
     if MARKER not in keys:
         raise ValueError("not a frozen U-Net file (marker key missing)")
     version = int(arc["format_version"])
-    if version != FORMAT_VERSION:
-        raise ValueError(f"frozen file format {version}, this build reads {FORMAT_VERSION}")
     dtype = str(arc["dtype"])
-    if dtype != "float16":
-        raise ValueError(f"frozen file dtype {dtype!r}: only float16 exists")
+    if dtype not in _FORMATS:
+        raise ValueError(f"frozen file dtype {dtype!r}: this build reads float16 (format 1) and int8 (format 2)")
+    if version != _FORMATS[dtype]:
+        raise ValueError(f"frozen file format {version} with dtype {dtype!r}: this build reads "
+                         f"format {_FORMATS[dtype]} for {dtype}")
     meta = {"input_size": tuple(int(v) for v in arc["input_size"]), "num_classes": int(arc["num_classes"]),
             "filters": tuple(int(v) for v in arc["filters"]), "dtype": dtype}
     folded = {k.replace(":", "/"): np.asarray(arc[k]) for k in keys if k not in _META}
@@ -161,6 +174,8 @@ def is_frozen_file(path) -> bool:
 class FrozenUNet:
     """A frozen fp16 copy of a U-Net: inference only, its own weights."""
 
+    DTYPE = "float16"
+
     def __init__(self, folded: Dict[str, np.ndarray], input_size, num_classes: int, filters, device=None):
         import torch
 
@@ -174,7 +189,7 @@ class FrozenUNet:
         if self.c > 4:
             raise ValueError(f"the image block takes at most 4 input channels, got {self.c}")
         self.num_classes = int(num_classes)
-        self.dtype = "float16"
+        self.dtype = self.DTYPE
         self.device = torch.device(device if device is not None else "cuda")
         self.folded = {k: np.array(v, copy=True) for k, v in folded.items()}  # Keras layouts, host
         self._dev: Dict[str, "torch.Tensor"] = {}
@@ -184,12 +199,22 @@ class FrozenUNet:
 
     # ------------------------------------------------------------------ construction ---
     @classmethod
-    def from_model(cls, model, dtype: str = "float16") -> "FrozenUNet":
-        if dtype != "float16":
-            raise ValueError(f"freeze(dtype={dtype!r}): float16 is the only frozen format")
+    def from_model(cls, model, dtype: str = "float16", calibration=None, batch_size=None) -> "FrozenUNet":
+        if dtype not in _FORMATS:
+            raise ValueError(f"freeze(dtype={dtype!r}): float16 and int8 are the frozen formats")
+        if dtype == "int8" and calibration is None:
+            raise ValueError("freeze(dtype='int8') needs calibration data (a representative dataset): "
+                             "pass calibration=images (N, H, W, C)")
         e = model.engine
-        folded = fold_weights(e.get_weights_dict(), e.num_classes, e.use_bn, e.filters)
-        return cls(folded, (e.h, e.w, e.c), e.num_classes, e.filters, e.device)
+        weights = e.get_weights_dict()
+        geom = ((e.h, e.w, e.c), e.num_classes, e.filters, e.device)
+        half = FrozenUNet(fold_weights(weights, e.num_classes, e.use_bn, e.filters), *geom)
+        if dtype == "float16":
+            return half
+        ranges = collect_ranges(half, calibration, batch_size)
+        half.release_buffers()
+        quant = quantize_weights(fold_exact(weights, e.num_classes, e.use_bn, e.filters), ranges, e.filters)
+        return FrozenUNetI8(quant, *geom)
 
     def _pack(self):
         """Device operands: pointwise kernels as [cout][cin] fp16 (k contiguous, the MFMA B
@@ -214,15 +239,17 @@ class FrozenUNet:
 
     # ---------------------------------------------------------------------- file i/o ---
     def archive(self) -> Dict[str, np.ndarray]:
-        return to_archive(self.folded, (self.h, self.w, self.c), self.num_classes, self.filters)
+        return to_archive(self.folded, (self.h, self.w, self.c), self.num_classes, self.filters, self.dtype)
 
     def save(self, path) -> None:
         save_archive(path, self.archive())
 
     @classmethod
     def load(cls, path, device=None) -> "FrozenUNet":
+        """The network of a frozen file, of the kind its dtype names (FrozenUNet or FrozenUNetI8)."""
         folded, meta = load_archive(path)
-        return cls(folded, meta["input_size"], meta["num_classes"], meta["filters"], device)
+        kind = FrozenUNetI8 if meta["dtype"] == "int8" else FrozenUNet
+        return kind(folded, meta["input_size"], meta["num_classes"], meta["filters"], device)
 
     # ----------------------------------------------------------------------- forward ---
     def _buffers(self, n: int) -> dict:
@@ -231,7 +258,7 @@ class FrozenUNet:
         b = self._bufs.get(n)
         if b is None:
             def e(*shape):
-                return torch.empty(shape, dtype=torch.float16, device=self.device)
+                return torch.empty(shape, dtype=self._act_dtype(), device=self.device)
             b = {"skip": [], "pool": []}
             h, w = self.h, self.w
             for f in self.filters:
@@ -242,6 +269,10 @@ class FrozenUNet:
             b["ping"] = [e(big), e(big)]
             self._bufs[n] = b
         return b
+
+    def _act_dtype(self):
+        import torch
+        return torch.float16
 
     def release_buffers(self):
         self._bufs.clear()
@@ -331,3 +362,254 @@ class FrozenUNet:
         outs = [self.forward(xt[i:i + bs]) for i in range(0, xt.shape[0], bs)]
         out = torch.cat(outs, 0) if len(outs) > 1 else outs[0]
         return out.cpu().numpy() if is_np else out
+
+
+# ------------------------------------------------------------------------ int8 format ---
+def calibration_names(filters: Sequence[int]):
+    """Every tensor whose range quantize_weights needs: the activations, and `<block>/y` (the
+    depthwise output, the int8 MFMA's A operand) for each block but the image block."""
+    return activation_names(filters) + [f"{b}/y" for b in block_names(filters) if b != IMAGE_BLOCK]
+
+
+def block_inputs(filters: Sequence[int]) -> Dict[str, Tuple[str, ...]]:
+    """{block: the activations its input is made of}: one name, or (upsample, skip) for a concat."""
+    n = len(filters)
+    src: Dict[str, Tuple[str, ...]] = {}
+    for i in range(n):
+        if i:
+            src[f"enc{i + 1}_block1"] = (f"enc{i}_pool",)
+        src[f"enc{i + 1}_block2"] = (f"enc{i + 1}_block1",)
+    src["bneck_block1"] = (f"enc{n}_pool",)
+    src["bneck_block2"] = ("bneck_block1",)
+    for i in range(n, 0, -1):
+        src[f"dec{i}_block1"] = (f"dec{i}_upsample", f"enc{i}_block2")
+        src[f"dec{i}_block2"] = (f"dec{i}_block1",)
+    return src
+
+
+def _scale(name: str, ranges, levels: int) -> float:
+    if name not in ranges:
+        raise ValueError(f"{name}: no calibration range")
+    r = float(ranges[name])
+    if not np.isfinite(r) or r < 0.0:
+        raise ValueError(f"{name}: calibration range {r!r} is negative or not finite")
+    return r / levels if r > 0.0 else 1.0
+
+
+def _quantize_rows(name: str, a: np.ndarray):
+    """a (..., k) float64 -> (int8 of the same shape, scale per row = max|row| / 127, 1 for a zero row)."""
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"{name}: folded values are not finite")
+    mx = np.abs(a).max(axis=-1)
+    s = np.where(mx > 0.0, mx / 127.0, 1.0)
+    q = np.clip(np.rint(a / s[..., None]), -127, 127).astype(np.int8)
+    return q, s
+
+
+def quantize_weights(exact: Dict[str, np.ndarray], ranges: Dict[str, float], filters: Sequence[int]
+                     ) -> Dict[str, np.ndarray]:
+    """The int8 network's operands from fold_exact(...) and the calibration ranges (max |.| of every
+    calibration_names tensor).  Pure NumPy, float64, rounded once at the end.  Per block `<b>/taps`
+    (fp32 [9][C] = dw s_in / s_y), `<b>/pw_q` (int8 [cout][C]), `<b>/mult`, `<b>/bias_q` (fp32 [cout]);
+    the image block keeps `/dw`, `/pw`, `/bias` in fp32; per upsample `/kernel_q` (int8, Keras
+    (2, 2, cout, cin)), `/colsum` (int32 [4 cout]), `/mult` (fp32 [4 cout]), `/bias_q` (fp32 [cout]);
+    `head/kernel` (fp32, the input scale folded in) and `head/bias`; `scale/<name>` (float64) for
+    every calibration_names tensor (uint8 max / 255 after a ReLU, int8 max / 127 for upsamples and
+    `<b>/y`, 1 for an all-zero tensor; a pool shares its block's scale).  ValueError names the
+    tensor whose range is missing, negative or not finite."""
+    filters = tuple(int(f) for f in filters)
+    for f in filters:
+        if f <= 0 or f % 32:
+            raise ValueError(f"filters {filters}: the int8 kernels need widths that are multiples of 32, got {f}")
+    n = len(filters)
+    ups = [f"dec{i + 1}_upsample" for i in range(n)]
+    scale: Dict[str, float] = {}
+    for name in calibration_names(filters):
+        signed = name in ups or name.endswith("/y")
+        scale[name] = _scale(name, ranges, 127 if signed else 255)
+    for i in range(n):  # the pool is the max of the block's bytes: one scale
+        scale[f"enc{i + 1}_pool"] = scale[f"enc{i + 1}_block2"]
+    out: Dict[str, np.ndarray] = {}
+    f32 = np.float32
+    inputs = block_inputs(filters)
+    for b in block_names(filters):
+        dw = np.asarray(exact[f"{b}_sepconv/depthwise_kernel"], np.float64)
+        pw = np.asarray(exact[f"{b}_sepconv/pointwise_kernel"], np.float64)[0, 0]  # (cin, cout)
+        bias = np.asarray(exact[f"{b}_sepconv/bias"], np.float64)
+        for nm, a in (("depthwise_kernel", dw), ("bias", bias)):
+            if not np.all(np.isfinite(a)):
+                raise ValueError(f"{b}_sepconv/{nm}: folded values are not finite")
+        s_out = scale[b]
+        if b == IMAGE_BLOCK:
+            if not np.all(np.isfinite(pw)):
+                raise ValueError(f"{b}_sepconv/pointwise_kernel: folded values are not finite")
+            out[f"{b}/dw"], out[f"{b}/pw"], out[f"{b}/bias"] = dw.astype(f32), pw.astype(f32), bias.astype(f32)
+            continue
+        s_in = np.concatenate([np.full(ch, scale[src]) for src, ch in
+                               zip(inputs[b], _split_channels(inputs[b], dw.shape[2]))])
+        s_y = scale[f"{b}/y"]
+        out[f"{b}/taps"] = (dw.reshape(9, -1) * s_in / s_y).astype(f32)
+        q, s_w = _quantize_rows(f"{b}_sepconv/pointwise_kernel", pw.T)
+        out[f"{b}/pw_q"] = np.ascontiguousarray(q)
+        out[f"{b}/mult"] = (s_y * s_w / s_out).astype(f32)
+        out[f"{b}/bias_q"] = (bias / s_out).astype(f32)
+    for i in range(n):
+        s = ups[i]
+        src = "bneck_block2" if i == n - 1 else f"dec{i + 2}_block2"
+        k = np.asarray(exact[f"{s}/kernel"], np.float64)  # (2, 2, cout, cin)
+        bias = np.asarray(exact[f"{s}/bias"], np.float64)
+        if not np.all(np.isfinite(bias)):
+            raise ValueError(f"{s}/bias: values are not finite")
+        q, s_w = _quantize_rows(f"{s}/kernel", k)
+        out[f"{s}/kernel_q"] = q
+        out[f"{s}/colsum"] = q.astype(np.int32).sum(axis=-1).reshape(-1).astype(np.int32)
+        out[f"{s}/mult"] = (scale[src] * s_w / scale[s]).reshape(-1).astype(f32)
+        out[f"{s}/bias_q"] = (bias / scale[s]).astype(f32)
+    hk = np.asarray(exact["output_mask/kernel"], np.float64)[0, 0]  # (cin, classes)
+    out["head/kernel"] = (hk * scale["dec1_block2"]).astype(f32)
+    out["head/bias"] = np.asarray(exact["output_mask/bias"], np.float64).astype(f32)
+    for name, v in scale.items():
+        out[f"scale/{name}"] = np.asarray(v, np.float64)
+    return out
+
+
+def _split_channels(sources, channels: int):
+    """Channel counts of a block input's sources: all of them, or (upsample, skip) halves."""
+    return (channels,) if len(sources) == 1 else (channels // 2, channels - channels // 2)
+
+
+def collect_ranges(model_or_frozen, x, batch_size: Optional[int] = None) -> Dict[str, float]:
+    """Calibration: max |.| of every calibration_names tensor over the images x (numpy array or
+    device tensor (N, H, W, C)).  Runs the fp16 FrozenUNet with keep_activations per batch and
+    keeps running maxima; each `<block>/y` is the fp32 depthwise 3x3 of the kept block input.
+    Needs the GPU; off the hot path."""
+    import torch
+    import torch.nn.functional as tf
+
+    from .metrics import as_device_tensor
+    net = model_or_frozen if isinstance(model_or_frozen, FrozenUNet) else FrozenUNet.from_model(model_or_frozen)
+    if net.dtype != "float16":
+        raise ValueError("collect_ranges runs the float16 frozen network")
+    xt = as_device_tensor(x, net.device)
+    if xt.dim() != 4 or xt.shape[0] == 0:
+        raise ValueError(f"calibration data must be (N, H, W, C) with N > 0, got {tuple(xt.shape)}")
+    bs = int(batch_size or 32)
+    names = activation_names(net.filters)
+    inputs = block_inputs(net.filters)
+    best: Dict[str, "torch.Tensor"] = {}
+
+    def track(name, t):
+        m = t.abs().max().float()
+        best[name] = m if name not in best else torch.maximum(best[name], m)
+
+    for i in range(0, xt.shape[0], bs):
+        net.forward(xt[i:i + bs], keep_activations=True)
+        for name in names:
+            track(name, net.activation(name))
+        for b, srcs in inputs.items():
+            a = torch.cat([net.activation(s) for s in srcs], dim=-1).float()
+            c = a.shape[-1]
+            dw = net._dev[f"{b}/dw"].view(3, 3, c).permute(2, 0, 1).reshape(c, 1, 3, 3).contiguous()
+            track(f"{b}/y", tf.conv2d(a.permute(0, 3, 1, 2).contiguous(), dw, padding=1, groups=c))
+    net._kept = {}
+    return {k: float(v.item()) for k, v in best.items()}
+
+
+class FrozenUNetI8(FrozenUNet):
+    """A frozen int8 copy of a U-Net (quantize_weights' operands on the kernels of
+    csrc/frozen_i8.hip): FrozenUNet's interface, one-byte activations.  activation(name) returns
+    the uint8 / int8 bytes q, activation_scale(name) the s of x = s q."""
+
+    DTYPE = "int8"
+
+    def _act_dtype(self):
+        import torch
+        return torch.uint8
+
+    def _pack(self):
+        import torch
+
+        def put(a):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+
+        f = self.folded
+        for name in calibration_names(self.filters):
+            if f"scale/{name}" not in f:
+                raise ValueError(f"int8 frozen network: scale/{name} is missing")
+        for k, v in f.items():
+            if not k.startswith("scale/"):
+                self._dev[k] = put(v.reshape(-1))
+
+    def activation_scale(self, name: str) -> float:
+        """s of x = s q for activation(name) (or for `<block>/y`)."""
+        if name not in calibration_names(self.filters):
+            raise KeyError(f"unknown activation {name!r}")
+        return float(self.folded[f"scale/{name}"])
+
+    def forward(self, x, keep_activations: bool = False):
+        """x: fp32 device tensor (N, H, W, C).  Returns fp32 probabilities (N, H, W, classes) in a
+        new tensor.  keep_activations: every layer's uint8 / int8 output stays readable by activation()."""
+        import torch
+
+        from . import ops
+        from .ops import I8View
+        if x.dim() != 4 or tuple(x.shape[1:]) != (self.h, self.w, self.c):
+            raise ValueError(f"expected input (N, {self.h}, {self.w}, {self.c}), got {tuple(x.shape)}")
+        n = int(x.shape[0])
+        d, fl = self._dev, self.filters
+        self._kept = {}
+        bufs = None if keep_activations else self._buffers(n)
+        state = {"cur": 0}
+
+        def new(name, h, w, c, fixed=None, signed=False):
+            dt = torch.int8 if signed else torch.uint8
+            if keep_activations:
+                t = torch.empty((n, h, w, c), dtype=dt, device=self.device)
+                self._kept[name] = t
+                return t
+            if fixed is not None:
+                return fixed
+            state["cur"] ^= 1
+            return bufs["ping"][state["cur"]][:n * h * w * c].view(dt).view(n, h, w, c)
+
+        def block(name, view, h, w, cout, out, pool=None):
+            ops.i8_sepconv(view, n, h, w, d[f"{name}/taps"], cout, d[f"{name}/pw_q"], d[f"{name}/mult"],
+                           d[f"{name}/bias_q"], out, pool)
+            return out
+
+        h, w = self.h, self.w
+        skips = []
+        a = None
+        for i, f in enumerate(fl):
+            s = f"enc{i + 1}"
+            out = new(f"{s}_block1", h, w, f)
+            if i == 0:
+                ops.i8_image_block(x, n, h, w, self.c, d[f"{s}_block1/dw"], f, d[f"{s}_block1/pw"],
+                                   d[f"{s}_block1/bias"], float(np.float32(self.folded[f"scale/{s}_block1"])), out)
+            else:
+                block(f"{s}_block1", I8View.plain(a), h, w, f, out)
+            skip = new(f"{s}_block2", h, w, f, None if bufs is None else bufs["skip"][i])
+            pool = new(f"{s}_pool", h // 2, w // 2, f, None if bufs is None else bufs["pool"][i])
+            block(f"{s}_block2", I8View.plain(out), h, w, f, skip, pool)
+            skips.append(skip)
+            a = pool
+            h, w = h // 2, w // 2
+        c = fl[-1] * 2
+        a = block("bneck_block1", I8View.plain(a), h, w, c, new("bneck_block1", h, w, c))
+        a = block("bneck_block2", I8View.plain(a), h, w, c, new("bneck_block2", h, w, c))
+        for i in range(len(fl)):
+            stage = len(fl) - i
+            f = fl[stage - 1]
+            s = f"dec{stage}"
+            up = new(f"{s}_upsample", 2 * h, 2 * w, f, signed=True)
+            ops.i8_conv_transpose2x2(a, n, h, w, c, f, d[f"{s}_upsample/kernel_q"], d[f"{s}_upsample/colsum"],
+                                     d[f"{s}_upsample/mult"], d[f"{s}_upsample/bias_q"], up)
+            h, w = 2 * h, 2 * w
+            a = block(f"{s}_block1", I8View.concat(up, skips[stage - 1]), h, w, f, new(f"{s}_block1", h, w, f))
+            a = block(f"{s}_block2", I8View.plain(a), h, w, f, new(f"{s}_block2", h, w, f))
+            c = f
+        prob = torch.empty((n, h, w, self.num_classes), dtype=torch.float32, device=self.device)
+        ops.i8_head(a, n, h, w, c, self.num_classes, d["head/kernel"], d["head/bias"], prob)
+        return prob
+
+    __call__ = forward

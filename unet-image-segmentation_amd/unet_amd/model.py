@@ -163,12 +163,15 @@ class UNetModel:
         out = torch.cat(outs, 0) if len(outs) > 1 else outs[0]
         return out.cpu().numpy() if is_np else out
 
-    def freeze(self, dtype: str = "float16"):
-        """A frozen half-precision inference copy (unet_amd.frozen.FrozenUNet): BatchNorm folded
-        into the pointwise weights, fp16 activations and MFMA operands.  It snapshots the weights:
-        later training does not change it.  float16 is the only format."""
+    def freeze(self, dtype: str = "float16", calibration=None, batch_size=None):
+        """A frozen inference copy (unet_amd.frozen.FrozenUNet): BatchNorm folded into the
+        pointwise weights.  It snapshots the weights: later training does not change it.
+        dtype "float16" (default): fp16 activations and MFMA operands.  dtype "int8": one-byte
+        activations and int8 MFMA operands (FrozenUNetI8), scaled by the ranges the network shows
+        on `calibration`, a representative set of images (numpy array or device tensor
+        (N, H, W, C)) run in batches of `batch_size`; ValueError without it."""
         from .frozen import FrozenUNet
-        return FrozenUNet.from_model(self, dtype)
+        return FrozenUNet.from_model(self, dtype, calibration, batch_size)
 
     def _log_values(self, res: torch.Tensor, prefix: str = "") -> Dict[str, float]:
         r = res.detach().cpu().numpy()

@@ -894,3 +894,112 @@ def f16_head(x: Tensor, n: int, h: int, w: int, cin: int, ncls: int, k: Tensor, 
     _call("unet_f16_head", (2.0 * m * cin * ncls, 2.0 * m * cin + 4.0 * m * ncls), _ptr(x), n, h, w, cin, ncls, _ptr(k),
           _ptr(bias), _ptr(prob), _stream())
     return prob
+
+
+# ------------------------------------------------------------------ frozen int8 (ABI 14) ---
+@dataclass
+class I8View:
+    """Python side of `unet_i8_view`: one quantised activation (uint8 after a ReLU, int8 after an
+    upsample), or the zero-copy concat of two; the dtype of each source tells its signedness."""
+
+    mode: int
+    src0: Tensor
+    c0: int
+    src1: Optional[Tensor] = None
+    c1: int = 0
+
+    @property
+    def channels(self) -> int:
+        return self.c0 + self.c1
+
+    @staticmethod
+    def plain(x: Tensor) -> "I8View":
+        return I8View(L.I8_VIEW_PLAIN, x, x.shape[-1])
+
+    @staticmethod
+    def concat(up: Tensor, skip: Tensor) -> "I8View":
+        return I8View(L.I8_VIEW_CONCAT, up, up.shape[-1], skip, skip.shape[-1])
+
+    @staticmethod
+    def _signed(t: Tensor, name: str) -> int:
+        if not isinstance(t, Tensor):
+            raise TypeError(f"{name}: expected a torch.Tensor")
+        if t.dtype not in (torch.uint8, torch.int8):
+            raise TypeError(f"{name}: expected torch.uint8 or torch.int8, got {t.dtype}")
+        return int(t.dtype == torch.int8)
+
+    def c_struct(self, n: int, h: int, w: int) -> L.UnetI8View:
+        v = L.UnetI8View()
+        v.mode = self.mode
+        v.c0 = self.c0
+        v.signed0 = self._signed(self.src0, "view.src0")
+        _check_dt(self.src0, "view.src0", self.src0.dtype, n * h * w * self.c0)
+        v.src0 = self.src0.data_ptr()
+        if self.mode == L.I8_VIEW_CONCAT:
+            v.signed1 = self._signed(self.src1, "view.src1")
+            _check_dt(self.src1, "view.src1", self.src1.dtype, n * h * w * self.c1)
+            v.c1 = self.c1
+            v.src1 = self.src1.data_ptr()
+        return v
+
+
+def i8_image_block(x: Tensor, n: int, h: int, w: int, cin: int, dk: Tensor, cout: int, pw: Tensor, bias: Tensor,
+                   out_scale: float, out: Tensor) -> Tensor:
+    """enc1_block1 of the int8 network on the unpadded fp32 image: out uint8 = clamp(rint(relu(.) / out_scale))."""
+    _check(x, "x", n * h * w * cin)
+    _check(dk, "depthwise_kernel", 9 * cin)
+    _check(pw, "pw_folded", cin * cout)
+    _check(bias, "bias", cout)
+    _check_dt(out, "out", torch.uint8, n * h * w * cout)
+    m = n * h * w
+    _call("unet_i8_image_block", (2.0 * m * cin * (9 + cout), 4.0 * m * cin + 1.0 * m * cout), _ptr(x), n, h, w, cin,
+          _ptr(dk), cout, _ptr(pw), _ptr(bias), float(out_scale), _ptr(out), _stream())
+    return out
+
+
+def i8_sepconv(x: I8View, n: int, h: int, w: int, taps: Tensor, cout: int, pw_q: Tensor, mult: Tensor, bias_q: Tensor,
+               out: Tensor, out_pool: Optional[Tensor] = None, route: int = 0) -> Tensor:
+    """A quantised conv block (the contract of include/unet_hip.h): taps fp32 [9][C], pw_q int8 [cout][C],
+    mult / bias_q fp32 [cout]; out uint8, out_pool (optional) its 2x2 max from the same launch."""
+    C = x.channels
+    _check(taps, "taps", 9 * C)
+    _check_dt(pw_q, "pw_q", torch.int8, C * cout)
+    _check(mult, "mult", cout)
+    _check(bias_q, "bias_q", cout)
+    _check_dt(out, "out", torch.uint8, n * h * w * cout)
+    if out_pool is not None:
+        _check_dt(out_pool, "out_pool", torch.uint8, n * (h // 2) * (w // 2) * cout)
+    vs = x.c_struct(n, h, w)
+    m = n * h * w
+    nb = 1.0 * m * (C + cout * (1.25 if out_pool is not None else 1.0)) + 1.0 * C * cout + 36.0 * C
+    _call("unet_i8_sepconv", (2.0 * m * C * (9 + cout), nb), ctypes.byref(vs), n, h, w, _ptr(taps), cout, _ptr(pw_q),
+          _ptr(mult), _ptr(bias_q), _ptr(out), _ptr(out_pool), int(route), _stream())
+    return out
+
+
+def i8_conv_transpose2x2(x: Tensor, n: int, h: int, w: int, cin: int, cout: int, k_q: Tensor, colsum: Tensor,
+                         mult: Tensor, bias_q: Tensor, out: Tensor) -> Tensor:
+    """Conv2DTranspose(2, strides 2) on uint8: k_q the Keras (2, 2, cout, cin) kernel as int8, colsum int32 and
+    mult fp32 per column [4 cout], bias_q fp32 [cout]; out int8, no activation."""
+    _check_dt(x, "x", torch.uint8, n * h * w * cin)
+    _check_dt(k_q, "kernel_q", torch.int8, 4 * cout * cin)
+    _check_dt(colsum, "colsum", torch.int32, 4 * cout)
+    _check(mult, "mult", 4 * cout)
+    _check(bias_q, "bias_q", cout)
+    _check_dt(out, "out", torch.int8, 4 * n * h * w * cout)
+    m = n * h * w
+    _call("unet_i8_conv_transpose2x2", (8.0 * m * cin * cout, 1.0 * m * (cin + 4 * cout) + 4.0 * cin * cout), _ptr(x),
+          n, h, w, cin, cout, _ptr(k_q), _ptr(colsum), _ptr(mult), _ptr(bias_q), _ptr(out), _stream())
+    return out
+
+
+def i8_head(x: Tensor, n: int, h: int, w: int, cin: int, ncls: int, k: Tensor, bias: Tensor, prob: Tensor) -> Tensor:
+    """Output layer on a uint8 input (its scale folded into k): fp32 probabilities (sigmoid / softmax)."""
+    _check_dt(x, "x", torch.uint8, n * h * w * cin)
+    _check(k, "kernel", cin * ncls)
+    _check(bias, "bias", ncls)
+    _check(prob, "prob", n * h * w * ncls)
+    m = n * h * w
+    _call("unet_i8_head", (2.0 * m * cin * ncls, 1.0 * m * cin + 4.0 * m * ncls), _ptr(x), n, h, w, cin, ncls, _ptr(k),
+          _ptr(bias), _ptr(prob), _stream())
+    return prob
