@@ -4,7 +4,8 @@ dataset that the converter names next).
 
 `fold_weights` is pure NumPy (float64): BatchNormalization (model/u_net.py:22-23, eps 1e-3) folds
 into the pointwise kernel and a bias, and the matrix-core operands are rounded to fp16.
-`FrozenUNet` runs the folded network on the fp16 kernels of csrc/frozen.hip: activations travel
+`FrozenUNet` runs the folded network on the fp16 kernels of csrc/frozen.hip (the fp16 precision of
+the kernel skeleton csrc/frozen_common.h): activations travel
 as fp16, already activated (ReLU at the producer, max-pool written by the producer), the
 pointwise GEMMs are one fp16 MFMA product per step with fp32 accumulation.
 
@@ -270,7 +271,8 @@ class FrozenUNet:
             self._bufs[n] = b
         return b
 
-    def _act_dtype(self):
+    def _act_dtype(self, signed: bool = False):
+        """dtype of an activation buffer (`signed`: an upsample's output)."""
         import torch
         return torch.float16
 
@@ -278,33 +280,58 @@ class FrozenUNet:
         self._bufs.clear()
         self._kept.clear()
 
+    # the per-layer launches: what a precision overrides
+    def _view(self):
+        from .ops import F16View
+        return F16View
+
+    def _image_block(self, name, x, n, h, w, cout, out):
+        from . import ops
+        d = self._dev
+        ops.f16_image_block(x, n, h, w, self.c, d[f"{name}/dw"], cout, d[f"{name}/pw"], d[f"{name}/bias"], out)
+
+    def _block(self, name, view, n, h, w, cout, out, pool=None):
+        from . import ops
+        d = self._dev
+        ops.f16_sepconv(view, n, h, w, d[f"{name}/dw"], cout, d[f"{name}/pw"], d[f"{name}/bias"], out, pool)
+
+    def _upsample(self, name, a, n, h, w, cin, cout, out):
+        from . import ops
+        d = self._dev
+        ops.f16_conv_transpose2x2(a, n, h, w, cin, cout, d[f"{name}/k"], d[f"{name}/bias"], out)
+
+    def _head(self, a, n, h, w, cin, prob):
+        from . import ops
+        d = self._dev
+        ops.f16_head(a, n, h, w, cin, self.num_classes, d["head/k"], d["head/bias"], prob)
+
     def forward(self, x, keep_activations: bool = False):
         """x: fp32 device tensor (N, H, W, C).  Returns fp32 probabilities (N, H, W, classes) in a
-        new tensor.  keep_activations: every layer's fp16 output stays readable by activation()."""
+        new tensor.  keep_activations: every layer's output (fp16; uint8 / int8 for the int8 network)
+        stays readable by activation()."""
         import torch
 
-        from . import ops
-        from .ops import F16View
         if x.dim() != 4 or tuple(x.shape[1:]) != (self.h, self.w, self.c):
             raise ValueError(f"expected input (N, {self.h}, {self.w}, {self.c}), got {tuple(x.shape)}")
         n = int(x.shape[0])
-        d, fl = self._dev, self.filters
+        fl, View = self.filters, self._view()
         self._kept = {}
         bufs = None if keep_activations else self._buffers(n)
         state = {"cur": 0}
 
-        def new(name, h, w, c, fixed=None):
+        def new(name, h, w, c, fixed=None, signed=False):
+            dt = self._act_dtype(signed)
             if keep_activations:
-                t = torch.empty((n, h, w, c), dtype=torch.float16, device=self.device)
+                t = torch.empty((n, h, w, c), dtype=dt, device=self.device)
                 self._kept[name] = t
                 return t
             if fixed is not None:
                 return fixed
             state["cur"] ^= 1
-            return bufs["ping"][state["cur"]][:n * h * w * c].view(n, h, w, c)
+            return bufs["ping"][state["cur"]][:n * h * w * c].view(dt).view(n, h, w, c)
 
         def block(name, view, h, w, cout, out, pool=None):
-            ops.f16_sepconv(view, n, h, w, d[f"{name}/dw"], cout, d[f"{name}/pw"], d[f"{name}/bias"], out, pool)
+            self._block(name, view, n, h, w, cout, out, pool)
             return out
 
         h, w = self.h, self.w
@@ -314,31 +341,30 @@ class FrozenUNet:
             s = f"enc{i + 1}"
             out = new(f"{s}_block1", h, w, f)
             if i == 0:
-                ops.f16_image_block(x, n, h, w, self.c, d[f"{s}_block1/dw"], f, d[f"{s}_block1/pw"],
-                                    d[f"{s}_block1/bias"], out)
+                self._image_block(f"{s}_block1", x, n, h, w, f, out)
             else:
-                block(f"{s}_block1", F16View.plain(a), h, w, f, out)
+                block(f"{s}_block1", View.plain(a), h, w, f, out)
             skip = new(f"{s}_block2", h, w, f, None if bufs is None else bufs["skip"][i])
             pool = new(f"{s}_pool", h // 2, w // 2, f, None if bufs is None else bufs["pool"][i])
-            block(f"{s}_block2", F16View.plain(out), h, w, f, skip, pool)
+            block(f"{s}_block2", View.plain(out), h, w, f, skip, pool)
             skips.append(skip)
             a = pool
             h, w = h // 2, w // 2
         c = fl[-1] * 2
-        a = block("bneck_block1", F16View.plain(a), h, w, c, new("bneck_block1", h, w, c))
-        a = block("bneck_block2", F16View.plain(a), h, w, c, new("bneck_block2", h, w, c))
+        a = block("bneck_block1", View.plain(a), h, w, c, new("bneck_block1", h, w, c))
+        a = block("bneck_block2", View.plain(a), h, w, c, new("bneck_block2", h, w, c))
         for i in range(len(fl)):
             stage = len(fl) - i
             f = fl[stage - 1]
             s = f"dec{stage}"
-            up = new(f"{s}_upsample", 2 * h, 2 * w, f)
-            ops.f16_conv_transpose2x2(a, n, h, w, c, f, d[f"{s}_upsample/k"], d[f"{s}_upsample/bias"], up)
+            up = new(f"{s}_upsample", 2 * h, 2 * w, f, signed=True)
+            self._upsample(f"{s}_upsample", a, n, h, w, c, f, up)
             h, w = 2 * h, 2 * w
-            a = block(f"{s}_block1", F16View.concat(up, skips[stage - 1]), h, w, f, new(f"{s}_block1", h, w, f))
-            a = block(f"{s}_block2", F16View.plain(a), h, w, f, new(f"{s}_block2", h, w, f))
+            a = block(f"{s}_block1", View.concat(up, skips[stage - 1]), h, w, f, new(f"{s}_block1", h, w, f))
+            a = block(f"{s}_block2", View.plain(a), h, w, f, new(f"{s}_block2", h, w, f))
             c = f
         prob = torch.empty((n, h, w, self.num_classes), dtype=torch.float32, device=self.device)
-        ops.f16_head(a, n, h, w, c, self.num_classes, d["head/k"], d["head/bias"], prob)
+        self._head(a, n, h, w, c, prob)
         return prob
 
     __call__ = forward
@@ -517,14 +543,14 @@ def collect_ranges(model_or_frozen, x, batch_size: Optional[int] = None) -> Dict
 
 class FrozenUNetI8(FrozenUNet):
     """A frozen int8 copy of a U-Net (quantize_weights' operands on the kernels of
-    csrc/frozen_i8.hip): FrozenUNet's interface, one-byte activations.  activation(name) returns
+    csrc/frozen_i8.hip): FrozenUNet's interface and graph walk, one-byte activations.  activation(name) returns
     the uint8 / int8 bytes q, activation_scale(name) the s of x = s q."""
 
     DTYPE = "int8"
 
-    def _act_dtype(self):
+    def _act_dtype(self, signed: bool = False):
         import torch
-        return torch.uint8
+        return torch.int8 if signed else torch.uint8
 
     def _pack(self):
         import torch
@@ -546,70 +572,29 @@ class FrozenUNetI8(FrozenUNet):
             raise KeyError(f"unknown activation {name!r}")
         return float(self.folded[f"scale/{name}"])
 
-    def forward(self, x, keep_activations: bool = False):
-        """x: fp32 device tensor (N, H, W, C).  Returns fp32 probabilities (N, H, W, classes) in a
-        new tensor.  keep_activations: every layer's uint8 / int8 output stays readable by activation()."""
-        import torch
-
-        from . import ops
+    def _view(self):
         from .ops import I8View
-        if x.dim() != 4 or tuple(x.shape[1:]) != (self.h, self.w, self.c):
-            raise ValueError(f"expected input (N, {self.h}, {self.w}, {self.c}), got {tuple(x.shape)}")
-        n = int(x.shape[0])
-        d, fl = self._dev, self.filters
-        self._kept = {}
-        bufs = None if keep_activations else self._buffers(n)
-        state = {"cur": 0}
+        return I8View
 
-        def new(name, h, w, c, fixed=None, signed=False):
-            dt = torch.int8 if signed else torch.uint8
-            if keep_activations:
-                t = torch.empty((n, h, w, c), dtype=dt, device=self.device)
-                self._kept[name] = t
-                return t
-            if fixed is not None:
-                return fixed
-            state["cur"] ^= 1
-            return bufs["ping"][state["cur"]][:n * h * w * c].view(dt).view(n, h, w, c)
+    def _image_block(self, name, x, n, h, w, cout, out):
+        from . import ops
+        d = self._dev
+        ops.i8_image_block(x, n, h, w, self.c, d[f"{name}/dw"], cout, d[f"{name}/pw"], d[f"{name}/bias"],
+                           float(np.float32(self.folded[f"scale/{name}"])), out)
 
-        def block(name, view, h, w, cout, out, pool=None):
-            ops.i8_sepconv(view, n, h, w, d[f"{name}/taps"], cout, d[f"{name}/pw_q"], d[f"{name}/mult"],
-                           d[f"{name}/bias_q"], out, pool)
-            return out
+    def _block(self, name, view, n, h, w, cout, out, pool=None):
+        from . import ops
+        d = self._dev
+        ops.i8_sepconv(view, n, h, w, d[f"{name}/taps"], cout, d[f"{name}/pw_q"], d[f"{name}/mult"],
+                       d[f"{name}/bias_q"], out, pool)
 
-        h, w = self.h, self.w
-        skips = []
-        a = None
-        for i, f in enumerate(fl):
-            s = f"enc{i + 1}"
-            out = new(f"{s}_block1", h, w, f)
-            if i == 0:
-                ops.i8_image_block(x, n, h, w, self.c, d[f"{s}_block1/dw"], f, d[f"{s}_block1/pw"],
-                                   d[f"{s}_block1/bias"], float(np.float32(self.folded[f"scale/{s}_block1"])), out)
-            else:
-                block(f"{s}_block1", I8View.plain(a), h, w, f, out)
-            skip = new(f"{s}_block2", h, w, f, None if bufs is None else bufs["skip"][i])
-            pool = new(f"{s}_pool", h // 2, w // 2, f, None if bufs is None else bufs["pool"][i])
-            block(f"{s}_block2", I8View.plain(out), h, w, f, skip, pool)
-            skips.append(skip)
-            a = pool
-            h, w = h // 2, w // 2
-        c = fl[-1] * 2
-        a = block("bneck_block1", I8View.plain(a), h, w, c, new("bneck_block1", h, w, c))
-        a = block("bneck_block2", I8View.plain(a), h, w, c, new("bneck_block2", h, w, c))
-        for i in range(len(fl)):
-            stage = len(fl) - i
-            f = fl[stage - 1]
-            s = f"dec{stage}"
-            up = new(f"{s}_upsample", 2 * h, 2 * w, f, signed=True)
-            ops.i8_conv_transpose2x2(a, n, h, w, c, f, d[f"{s}_upsample/kernel_q"], d[f"{s}_upsample/colsum"],
-                                     d[f"{s}_upsample/mult"], d[f"{s}_upsample/bias_q"], up)
-            h, w = 2 * h, 2 * w
-            a = block(f"{s}_block1", I8View.concat(up, skips[stage - 1]), h, w, f, new(f"{s}_block1", h, w, f))
-            a = block(f"{s}_block2", I8View.plain(a), h, w, f, new(f"{s}_block2", h, w, f))
-            c = f
-        prob = torch.empty((n, h, w, self.num_classes), dtype=torch.float32, device=self.device)
-        ops.i8_head(a, n, h, w, c, self.num_classes, d["head/kernel"], d["head/bias"], prob)
-        return prob
+    def _upsample(self, name, a, n, h, w, cin, cout, out):
+        from . import ops
+        d = self._dev
+        ops.i8_conv_transpose2x2(a, n, h, w, cin, cout, d[f"{name}/kernel_q"], d[f"{name}/colsum"], d[f"{name}/mult"],
+                                 d[f"{name}/bias_q"], out)
 
-    __call__ = forward
+    def _head(self, a, n, h, w, cin, prob):
+        from . import ops
+        d = self._dev
+        ops.i8_head(a, n, h, w, cin, self.num_classes, d["head/kernel"], d["head/bias"], prob)

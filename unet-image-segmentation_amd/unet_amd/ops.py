@@ -804,8 +804,9 @@ def _check_dt(t: Tensor, name: str, dtype, numel: Optional[int] = None):
 
 
 @dataclass
-class F16View:
-    """Python side of `unet_f16_view`: one fp16 activation, or the zero-copy concat of two."""
+class _FrozenView:
+    """One frozen activation, or the zero-copy concat of two (upsample, skip); the subclasses add
+    the mode values and `c_struct`, the C view of their precision."""
 
     mode: int
     src0: Tensor
@@ -817,13 +818,19 @@ class F16View:
     def channels(self) -> int:
         return self.c0 + self.c1
 
-    @staticmethod
-    def plain(x: Tensor) -> "F16View":
-        return F16View(L.F16_VIEW_PLAIN, x, x.shape[-1])
+    @classmethod
+    def plain(cls, x: Tensor):
+        return cls(cls.PLAIN, x, x.shape[-1])
 
-    @staticmethod
-    def concat(up: Tensor, skip: Tensor) -> "F16View":
-        return F16View(L.F16_VIEW_CONCAT, up, up.shape[-1], skip, skip.shape[-1])
+    @classmethod
+    def concat(cls, up: Tensor, skip: Tensor):
+        return cls(cls.CONCAT, up, up.shape[-1], skip, skip.shape[-1])
+
+
+class F16View(_FrozenView):
+    """Python side of `unet_f16_view`: fp16 sources."""
+
+    PLAIN, CONCAT = L.F16_VIEW_PLAIN, L.F16_VIEW_CONCAT
 
     def c_struct(self, n: int, h: int, w: int) -> L.UnetF16View:
         _check_dt(self.src0, "view.src0", torch.float16, n * h * w * self.c0)
@@ -897,28 +904,11 @@ def f16_head(x: Tensor, n: int, h: int, w: int, cin: int, ncls: int, k: Tensor, 
 
 
 # ------------------------------------------------------------------ frozen int8 (ABI 14) ---
-@dataclass
-class I8View:
-    """Python side of `unet_i8_view`: one quantised activation (uint8 after a ReLU, int8 after an
-    upsample), or the zero-copy concat of two; the dtype of each source tells its signedness."""
+class I8View(_FrozenView):
+    """Python side of `unet_i8_view`: quantised sources (uint8 after a ReLU, int8 after an upsample);
+    the dtype of each source tells its signedness."""
 
-    mode: int
-    src0: Tensor
-    c0: int
-    src1: Optional[Tensor] = None
-    c1: int = 0
-
-    @property
-    def channels(self) -> int:
-        return self.c0 + self.c1
-
-    @staticmethod
-    def plain(x: Tensor) -> "I8View":
-        return I8View(L.I8_VIEW_PLAIN, x, x.shape[-1])
-
-    @staticmethod
-    def concat(up: Tensor, skip: Tensor) -> "I8View":
-        return I8View(L.I8_VIEW_CONCAT, up, up.shape[-1], skip, skip.shape[-1])
+    PLAIN, CONCAT = L.I8_VIEW_PLAIN, L.I8_VIEW_CONCAT
 
     @staticmethod
     def _signed(t: Tensor, name: str) -> int:
