@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UNET_ABI_VERSION 14
+#define UNET_ABI_VERSION 15
 
 typedef void* unet_stream_t; /* hipStream_t */
 
@@ -645,6 +645,45 @@ int unet_i8_conv_transpose2x2(const unsigned char* x, int n, int h, int w, int c
  * input scale folded in, fp32 bias, fp32 prob = sigmoid (ncls == 1) or softmax.                */
 int unet_i8_head(const unsigned char* x, int n, int h, int w, int cin, int ncls,
                  const float* kernel, const float* bias, float* prob, unet_stream_t stream);
+
+/* ----- Device-side image pipeline (ABI 15) ---------------------------------------------------
+ * The CLIs' image steps around the forward, which the reference does with cv2 on the host:
+ * scripts/inference.py:105-108 and scripts/benchmark.py:105 (cv2.resize of the decoded image to
+ * the model size, INTER_LINEAR, then / 255.0), and scripts/inference.py:147-160 (cv2.resize of the
+ * probability map back to the image's size, INTER_LINEAR, then > threshold -> 255).
+ *
+ * Sampling coordinates come from the host (unet_amd/imageproc.py: linear_coords, float64, half-pixel
+ * centres with edge clamping), one table per axis with one entry per OUTPUT row / column:
+ * source indices i0 <= i1 and the fp32 weight of i1.  The same function feeds the NumPy path, so
+ * the two cannot drift apart.
+ *
+ * THE ARITHMETIC CONTRACT, every operation rounded to fp32 and none contracted into an fma (this
+ * object is built with -ffp-contract=off), for the four taps a = s[y.i0][x.i0], b = s[y.i0][x.i1],
+ * c = s[y.i1][x.i0], d = s[y.i1][x.i1]:
+ *   top = a + (b - a) * x.frac;  bot = c + (d - c) * x.frac;  out = top + (bot - top) * y.frac
+ * which is bitwise what resize_linear (unet_amd/imageproc.py) computes in NumPy.                 */
+typedef struct unet_lerp_coord {
+    int32_t i0;       /* first source index, 0 <= i0 < n_in                 */
+    int32_t i1;       /* second source index, min(i0 + 1, n_in - 1)         */
+    float frac;       /* weight of i1, in [0, 1)                            */
+    int32_t reserved; /* 0; keeps an entry one 16-byte load                 */
+} unet_lerp_coord;
+
+/* uint8 image (sh, sw, c), c = 1 or 3, densely packed (rows at any byte alignment) -> fp32
+ * (oh, ow, c) at dst: s = (float)byte / 255.0f (correctly rounded), then the contract above per
+ * channel.  reverse_channels != 0 reads source channel c - 1 - k for output channel k (RGB as
+ * decoded -> the BGR the reference feeds).  ytab has oh entries, xtab ow; dst is the caller's slot
+ * inside an (N, oh, ow, c) batch tensor.  Equals resize_linear(img.astype(float32) / 255, oh, ow). */
+int unet_image_resize_u8(const unsigned char* src, int sh, int sw, int c,
+                         const unet_lerp_coord* ytab, const unet_lerp_coord* xtab, int oh, int ow,
+                         int reverse_channels, float* dst, unet_stream_t stream);
+/* fp32 probabilities (h, w, ncls) of one image -> uint8 mask (oh, ow), exactly oh * ow bytes at any
+ * byte alignment.  ncls == 1: 255 where the interpolated probability > threshold (strict), else 0.
+ * 1 < ncls <= 255: the index of the largest interpolated class probability, the first on ties
+ * (np.argmax); threshold is ignored.                                                             */
+int unet_mask_resize(const float* prob, int h, int w, int ncls, const unet_lerp_coord* ytab,
+                     const unet_lerp_coord* xtab, int oh, int ow, float threshold,
+                     unsigned char* mask, unet_stream_t stream);
 
 #ifdef __cplusplus
 }

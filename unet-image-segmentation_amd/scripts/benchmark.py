@@ -16,6 +16,10 @@ Same flags and defaults (reference scripts/benchmark.py:59-93), same validation 
 The forward runs on the GPU in batches (inference BatchNorm uses the moving statistics, so a
 sample's output does not depend on its batch); the confusion counts accumulate on the device
 (unet_meaniou_update).  OpenCV steps are restated in unet_amd/imageproc.py.
+
+--device_imageproc (an extra of this port, off by default) runs the images' /255 and resize on the
+device, a batch at a time (unet_amd/pipeline.py: preprocess_images), bitwise the same arithmetic,
+so every number printed is the same; the truth masks are still rasterised on the host.
 """
 import argparse
 import json
@@ -51,16 +55,23 @@ def parse_args(argv=None) -> argparse.Namespace:
                         help="Threshold (0-1) to convert model's probability prediction to a binary mask.")
     parser.add_argument("--low_score_log", type=str, default=None,
                         help="Optional file path to save the list of files scoring below the iou_threshold.")
+    parser.add_argument("--device_imageproc", action="store_true",
+                        help="Scale and resize the images on the GPU (same numbers, less host time).")
     return parser.parse_args(argv)
 
 
-def _read_bgr(path: str) -> Optional[np.ndarray]:
+def _read_rgb(path: str) -> Optional[np.ndarray]:
     from PIL import Image
     try:
         with Image.open(path) as im:
-            return np.asarray(im.convert("RGB"))[..., ::-1]
+            return np.asarray(im.convert("RGB"))
     except Exception:
         return None
+
+
+def _read_bgr(path: str) -> Optional[np.ndarray]:
+    rgb = _read_rgb(path)
+    return None if rgb is None else rgb[..., ::-1]
 
 
 def load_image_for_predict(img_path: str) -> Optional[np.ndarray]:
@@ -128,8 +139,11 @@ def find_pairs(images_root: str, gtruth_root: str) -> Tuple[List[Dict], int]:
     return pairs, skipped
 
 
-def evaluate(model, pairs: List[Dict], pred_threshold: float, iou_threshold: float, device=None):
-    """Overall MeanIoU(2) and the (file_id, sample IoU) pairs below iou_threshold."""
+def evaluate(model, pairs: List[Dict], pred_threshold: float, iou_threshold: float, device=None,
+             device_imageproc: bool = False):
+    """Overall MeanIoU(2) and the (file_id, sample IoU) pairs below iou_threshold.
+    device_imageproc: a batch entry holds the decoded RGB image, and load_image_for_predict's
+    scaling and resize run on the device for the whole batch at once."""
     import torch
     from unet_amd.metrics import MeanIoU
     miou = MeanIoU(num_classes=2, name="overall_mean_iou", threshold=pred_threshold, device=device)
@@ -139,9 +153,14 @@ def evaluate(model, pairs: List[Dict], pred_threshold: float, iou_threshold: flo
     def flush():
         if not batch:
             return
-        x = np.concatenate([b[1] for b in batch])
         yt = np.concatenate([b[2] for b in batch]).astype(np.float32)
-        prob = model.predict(x) if device is None else model.predict(torch.as_tensor(x, device=device))
+        if device_imageproc:
+            from unet_amd.pipeline import model_geometry, preprocess_images
+            h, w, c, _, dev = model_geometry(model)
+            prob = model.predict(preprocess_images([b[1] for b in batch], (h, w, c), dev, bgr=True))
+        else:
+            x = np.concatenate([b[1] for b in batch])
+            prob = model.predict(x) if device is None else model.predict(torch.as_tensor(x, device=device))
         prob_t = torch.as_tensor(prob, device=miou.device)
         miou.update_state(torch.as_tensor(yt, device=miou.device), prob_t)  # p > thr on the device
         pred = (prob_t > pred_threshold).to(torch.uint8).cpu().numpy()
@@ -154,7 +173,12 @@ def evaluate(model, pairs: List[Dict], pred_threshold: float, iou_threshold: flo
 
     for i, pair in enumerate(pairs):
         print(f"\rProcessing [{i + 1}/{len(pairs)}]: {pair['id']}", end="")
-        img = load_image_for_predict(pair["image"])
+        if device_imageproc:
+            img = _read_rgb(pair["image"])
+            if img is None:
+                print(f"Warning: Could not read image: {pair['image']}. Skipping.")
+        else:
+            img = load_image_for_predict(pair["image"])
         truth = build_mask_from_quad(pair["json"], IMG_HEIGHT, IMG_WIDTH)
         if img is None or truth is None:
             print(f"\nSkipping pair due to loading error: {pair['id']}")
@@ -209,7 +233,8 @@ def main(argv=None):
         sys.exit(1)
     print(f"Prepared {len(pairs)} image/JSON pairs for evaluation ({skipped} images skipped).")
     print(f"Evaluating model (Prediction Threshold: {args.pred_threshold:.2f})...")
-    final, low = evaluate(model, pairs, args.pred_threshold, args.iou_threshold)
+    final, low = evaluate(model, pairs, args.pred_threshold, args.iou_threshold,
+                          device_imageproc=args.device_imageproc)
     print("\nEvaluation complete.")
     print(f"\n{'=' * 30}")
     print(f"Overall Mean IoU: {final:.4f}")

@@ -11,6 +11,11 @@ unet_amd/imageproc.py restates cv2.resize INTER_LINEAR (half-pixel centres, no a
 findContours(RETR_EXTERNAL) + contourArea (shoelace area of the traced boundary-pixel chain,
 holes included) + boundingRect.  The reference's own sample output (samples/usage) pins the
 crop (tests/test_imageproc.py).  This post-processing is off the GPU path.
+
+--device_imageproc (an extra of this port, off by default) runs the two resizes and the threshold
+on the device instead (model.predict_masks: unet_amd/pipeline.py), bitwise the same arithmetic,
+so the mask and the crop are byte-identical to the default path's; the contour and the crop stay
+on the host.
 """
 import argparse
 import os
@@ -41,6 +46,8 @@ def parse_args(argv=None) -> argparse.Namespace:
                         help="Threshold value (0.0 to 1.0) to convert probability mask to binary mask.")
     parser.add_argument("--min_area", type=float, default=MIN_CONTOUR_AREA,
                         help=f"Minimum contour area threshold for cropping (default: {MIN_CONTOUR_AREA}).")
+    parser.add_argument("--device_imageproc", action="store_true",
+                        help="Resize the image and the probability map on the GPU (same result, less host time).")
     return parser.parse_args(argv)
 
 
@@ -71,10 +78,14 @@ def predict_mask(model, input_tensor):
 
 
 def postprocess_and_save_results(prob, original_bgr, orig_h, orig_w, out_mask, out_crop, thr=0.5, min_area=100.0):
-    from PIL import Image
     print("Processing predicted mask...")
     resized = resize_linear(prob[..., 0], orig_h, orig_w)
     binary = (resized > thr).astype(np.uint8) * 255
+    save_mask_and_crop(binary, original_bgr, out_mask, out_crop, min_area)
+
+
+def save_mask_and_crop(binary, original_bgr, out_mask, out_crop, min_area=100.0):
+    from PIL import Image
     print(f"Saving binary mask to {out_mask} ...")
     if os.path.dirname(out_mask):
         os.makedirs(os.path.dirname(out_mask), exist_ok=True)
@@ -94,6 +105,27 @@ def postprocess_and_save_results(prob, original_bgr, orig_h, orig_w, out_mask, o
     if os.path.dirname(out_crop):
         os.makedirs(os.path.dirname(out_crop), exist_ok=True)
     Image.fromarray(np.ascontiguousarray(crop)).save(out_crop)
+
+
+def run_on_device(model, args):
+    """--device_imageproc: the decoded RGB image goes to the device as it is; scaling, both resizes
+    and the threshold run there (predict_masks reverses the channels: the network is fed BGR)."""
+    from PIL import Image
+    print(f"Loading image: {args.input} ...")
+    try:
+        rgb = np.asarray(Image.open(args.input).convert("RGB"))
+    except Exception:
+        print(f"Error: Could not read image from {args.input}")
+        sys.exit(1)
+    print("Running prediction...")
+    try:
+        binary = model.predict_masks([rgb], threshold=args.threshold, bgr=True)[0]
+    except Exception as e:
+        print(f"Error during model prediction: {e}")
+        sys.exit(1)
+    print("Postprocessing results...")
+    print("Processing predicted mask...")
+    save_mask_and_crop(binary, rgb[..., ::-1], args.output_mask, args.output_cropped, args.min_area)
 
 
 def main(argv=None):
@@ -122,6 +154,10 @@ def main(argv=None):
         print("\n--- Error loading model ---")
         print(f"{e}")
         sys.exit(1)
+    if args.device_imageproc:
+        run_on_device(model, args)
+        print("Inference script finished.")
+        return
     print(f"Loading and preprocessing image: {args.input} ...")
     x, bgr, h, w = load_and_preprocess_image(args.input, IMG_HEIGHT, IMG_WIDTH)
     if x is None:

@@ -12,7 +12,7 @@ from pathlib import Path
 
 LIB_NAME = "libunet_hip.so"
 LIB_PATH = Path(os.environ.get("UNET_HIP_LIB", Path(__file__).with_name(LIB_NAME)))
-ABI_VERSION = 14
+ABI_VERSION = 15
 SPLIT_MAX_SEGS = 64  # UNET_SPLIT_MAX_SEGS
 
 VIEW_PLAIN, VIEW_BNRELU, VIEW_POOL_BNRELU, VIEW_CONCAT = 0, 1, 2, 3
@@ -160,6 +160,8 @@ SIGNATURES = {
     "unet_i8_sepconv": (c_int, [_QVP, c_int, c_int, c_int, P, c_int, P, P, P, P, P, c_int, P]),
     "unet_i8_conv_transpose2x2": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P]),
     "unet_i8_head": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "unet_image_resize_u8": (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_int, c_int, P, P]),
+    "unet_mask_resize": (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_int, c_float, P, P]),
 }
 
 _lib = None

@@ -27,19 +27,23 @@ import numpy as np
 _DIRS = ((0, 1), (-1, 1), (-1, 0), (-1, -1), (0, -1), (1, -1), (1, 0), (1, 1))
 
 
+def linear_coords(n_out: int, n_in: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """INTER_LINEAR's sampling of one axis: for each of n_out output positions the two source
+    indices i0 <= i1 (int64) and the float32 weight of i1.  Half-pixel centres, clamped to the
+    edge, computed in float64.  resize_linear and the device kernels (ops.image_resize_u8,
+    ops.mask_resize, through pipeline.coord_table) both take their coordinates from here."""
+    s = (np.arange(n_out) + 0.5) * (n_in / n_out) - 0.5
+    s = np.clip(s, 0, n_in - 1)
+    i0 = np.floor(s).astype(np.int64)
+    i1 = np.minimum(i0 + 1, n_in - 1)
+    return i0, i1, (s - i0).astype(np.float32)
+
+
 def resize_linear(img: np.ndarray, out_h: int, out_w: int) -> np.ndarray:
     """cv2.resize(img, (out_w, out_h), interpolation=INTER_LINEAR) for float images."""
     h, w = img.shape[:2]
-
-    def coords(n_out, n_in):
-        s = (np.arange(n_out) + 0.5) * (n_in / n_out) - 0.5
-        s = np.clip(s, 0, n_in - 1)
-        i0 = np.floor(s).astype(np.int64)
-        i1 = np.minimum(i0 + 1, n_in - 1)
-        return i0, i1, (s - i0).astype(np.float32)
-
-    y0, y1, fy = coords(out_h, h)
-    x0, x1, fx = coords(out_w, w)
+    y0, y1, fy = linear_coords(out_h, h)
+    x0, x1, fx = linear_coords(out_w, w)
     a = img[y0][:, x0]
     b = img[y0][:, x1]
     c = img[y1][:, x0]

@@ -993,3 +993,59 @@ def i8_head(x: Tensor, n: int, h: int, w: int, cin: int, ncls: int, k: Tensor, b
     _call("unet_i8_head", (2.0 * m * cin * ncls, 1.0 * m * cin + 4.0 * m * ncls), _ptr(x), n, h, w, cin, ncls, _ptr(k),
           _ptr(bias), _ptr(prob), _stream())
     return prob
+
+
+# ------------------------------------------------------------- device-side image pipeline ---
+def _check_table(t: Tensor, name: str, n: int):
+    """A sampling table of n `unet_lerp_coord` entries: int32 (n, 4) = i0, i1, frac bits, 0."""
+    _check_dt(t, name, torch.int32, 4 * n)
+    if t.dim() != 2 or t.shape[1] != 4:
+        raise ValueError(f"{name}: expected shape ({n}, 4), got {tuple(t.shape)}")
+
+
+def image_resize_u8(src: Tensor, ytab: Tensor, xtab: Tensor, out: Tensor, slot: int = 0,
+                    reverse_channels: bool = False) -> Tensor:
+    """uint8 image (sh, sw, c), c = 1 or 3 -> out[slot] of the fp32 batch tensor (N, oh, ow, c):
+    bitwise imageproc.resize_linear(img.astype(float32) / 255, oh, ow), the channels reversed first
+    if asked.  ytab / xtab: pipeline.coord_table(oh, sh) / (ow, sw)."""
+    _check_dt(src, "src", torch.uint8)
+    _check(out, "out")
+    if src.dim() != 3 or src.shape[2] not in (1, 3):
+        raise ValueError(f"src: expected a (h, w, 1 or 3) image, got {tuple(src.shape)}")
+    sh, sw, c = (int(v) for v in src.shape)
+    if out.dim() != 4 or out.shape[3] != c:
+        raise ValueError(f"out: expected (N, oh, ow, {c}), got {tuple(out.shape)}")
+    n, oh, ow = (int(v) for v in out.shape[:3])
+    if not 0 <= slot < n:
+        raise ValueError(f"slot {slot} outside a batch of {n}")
+    if min(sh, sw, oh, ow) < 1:
+        raise ValueError(f"empty image: source {sh}x{sw}, destination {oh}x{ow}")
+    _check_table(ytab, "ytab", oh)
+    _check_table(xtab, "xtab", ow)
+    px = oh * ow
+    dst = ctypes.c_void_p(out.data_ptr() + 4 * slot * px * c)
+    _call("unet_image_resize_u8", (18.0 * px * c, 4.0 * px * c + float(min(sh * sw, 4 * px)) * c), _ptr(src), sh, sw,
+          c, _ptr(ytab), _ptr(xtab), oh, ow, int(bool(reverse_channels)), dst, _stream())
+    return out
+
+
+def mask_resize(prob: Tensor, ytab: Tensor, xtab: Tensor, out: Tensor, threshold: float = 0.5) -> Tensor:
+    """fp32 probabilities (h, w, ncls) of one image -> uint8 mask out (oh, ow): 255 where the
+    bilinearly resized probability > threshold (ncls == 1), else the argmax class index; bitwise the
+    host's resize_linear + compare / np.argmax.  ytab / xtab: pipeline.coord_table(oh, h) / (ow, w)."""
+    _check(prob, "prob")
+    _check_dt(out, "out", torch.uint8)
+    if prob.dim() != 3 or out.dim() != 2:
+        raise ValueError(f"expected prob (h, w, ncls) and out (oh, ow), got {tuple(prob.shape)}, {tuple(out.shape)}")
+    h, w, ncls = (int(v) for v in prob.shape)
+    oh, ow = (int(v) for v in out.shape)
+    if not 1 <= ncls <= 255:
+        raise ValueError(f"ncls must be 1..255 (the mask holds a uint8 class index), got {ncls}")
+    if min(h, w, oh, ow) < 1:
+        raise ValueError(f"empty image: source {h}x{w}, destination {oh}x{ow}")
+    _check_table(ytab, "ytab", oh)
+    _check_table(xtab, "xtab", ow)
+    px = oh * ow
+    _call("unet_mask_resize", (9.0 * px * ncls, 1.0 * px + 4.0 * h * w * ncls), _ptr(prob), h, w, ncls, _ptr(ytab),
+          _ptr(xtab), oh, ow, float(threshold), _ptr(out), _stream())
+    return out
