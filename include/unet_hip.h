@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UNET_ABI_VERSION 15
+#define UNET_ABI_VERSION 16
 
 typedef void* unet_stream_t; /* hipStream_t */
 
@@ -684,6 +684,47 @@ int unet_image_resize_u8(const unsigned char* src, int sh, int sw, int c,
 int unet_mask_resize(const float* prob, int h, int w, int ncls, const unet_lerp_coord* ytab,
                      const unet_lerp_coord* xtab, int oh, int ow, float threshold,
                      unsigned char* mask, unet_stream_t stream);
+
+/* ----- Device-side largest-contour box (ABI 16) ----------------------------------------------
+ * The last step of scripts/inference.py (reference :173-187): cv2.findContours(mask, RETR_EXTERNAL,
+ * CHAIN_APPROX_SIMPLE), the contour of largest cv2.contourArea (the first on ties), its
+ * cv2.boundingRect.  unet_amd/imageproc.py: largest_external_contour traces the borders on the
+ * host; border following is serial, so the kernels compute a closed form that equals it exactly.
+ *
+ * THE CONTRACT.  Foreground is mask != 0; the image outside its frame is background.
+ *   O  the outer background: the background pixels that reach the frame through background
+ *      4-neighbours.  F, the filled image, is everything else: the foreground, its holes, and any
+ *      component nested inside a hole.
+ *   The 8-connected components of F are the external contours, one to one, in the order of their
+ *   first pixel in raster order.  Per component:
+ *      boundingRect  its bounding box (x, y, w, h);
+ *      area2         twice its contourArea, an integer: the sum over the 2x2 pixel cells that lie
+ *                    wholly inside the image of 2 [all four pixels in F] + [exactly three in F]
+ *                    (a cell with three or more F pixels lies in one component).
+ *   Selection: the largest area2; on ties the component whose first raster pixel has the smallest
+ *   linear index (also when every area is 0).  No foreground: count = 0 and every field 0.
+ * Every value is an integer and no result depends on the order in which blocks or atomics arrive:
+ * the record is deterministic.  unet_amd/imageproc.py: external_contour_stats_filled restates the
+ * contract in NumPy; tests/test_contour_host.py holds it equal to the tracer.                    */
+typedef struct unet_contour_box {
+    int32_t count;      /* external contours found; 0: the other fields are 0 */
+    int32_t x, y, w, h; /* boundingRect of the selected contour */
+    int32_t first;      /* linear index y*W+x of its first pixel in raster order */
+    int64_t area2;      /* twice its contourArea */
+} unet_contour_box;     /* 32 bytes */
+
+/* Bytes of workspace unet_mask_largest_contour needs for an (h, w) mask, a multiple of 256: int32
+ * labels, int32 area sums and one byte per pixel, behind a 256-byte header.  0 for sizes the call
+ * refuses.                                                                                      */
+size_t unet_mask_largest_contour_workspace(int h, int w);
+/* mask: h * w densely packed bytes at any byte alignment.  out: device memory, 8-byte aligned,
+ * written in full by the call (no pre-zeroing asked of the caller).  ws: device memory, 16-byte
+ * aligned, ws_bytes >= the query's answer; its contents before the call do not matter and no byte
+ * beyond the query's answer is touched.  Refused with an error message: a null pointer, h < 1 or
+ * w < 1, h * w > 2^30 (linear indices and area2 are kept in int32), a short workspace.  Ten small
+ * launches on `stream`; no kernel waits for another workgroup.                                  */
+int unet_mask_largest_contour(const unsigned char* mask, int h, int w, unet_contour_box* out,
+                              void* ws, size_t ws_bytes, unet_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,19 @@ Per row, ms per image:
 The last line times what stays on the host after either path, the contour / crop search
 (imageproc.largest_external_contour), on the reference's two 960x540 sample masks
 (--only-contour prints that line alone).
+
+    python tools/bench_imageproc.py --contour [--reps 5] > profiles/contour_predict.txt
+
+prints the device contour section instead (csrc/contour.hip, predict_masks(..., return_boxes=True)):
+  per mask (the two 960x540 sample masks; one of them enlarged, nearest neighbour, to 1080x1920 and
+  3000x4000): device_ms, HIP-event time around the ten launches of ops.mask_largest_contour alone
+  (median); tracer_ms, imageproc.largest_external_contour on the host in the same run (timed once
+  when it takes more than 2 s); filled_ms, the NumPy closed form, from 1080x1920 up; and whether
+  the device record equals the host's answer;
+  per size and batch: predict_masks end to end (host clock, masks and boxes in host memory), ms per
+  image, without and with return_boxes, alternating; the host tracer (960x540 only: the network has
+  random weights) and the closed form on the masks that came back, and whether the boxes equal the
+  closed form's.
 """
 import argparse
 import json
@@ -106,15 +119,107 @@ def contour_remainder(reps):
     print(json.dumps(rec), flush=True)
 
 
+def _median_ms(fn, reps, once_above=2.0):
+    t0 = time.perf_counter()
+    out = fn()
+    first = time.perf_counter() - t0
+    ts = [first]
+    if first <= once_above:
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            ts.append(time.perf_counter() - t0)
+    return 1e3 * float(np.median(ts)), out
+
+
+def contour_section(reps, sizes, batches):
+    from PIL import Image
+
+    from unet_amd.imageproc import largest_external_contour_filled, resize_nearest
+    from unet_amd.pipeline import decode_contour_box
+    assert torch.cuda.is_available(), "bench_imageproc needs the MI355X"
+    print(f"# {torch.cuda.get_device_name(0)}; torch {torch.__version__}; reps {reps}", flush=True)
+    print("# device contour step per mask: HIP-event ms of the launches alone | host tracer | NumPy closed form",
+          flush=True)
+    names = ("brazil_passport", "chile_id_card")
+    sample = [np.asarray(Image.open(os.path.join(SAMPLES, "usage", n + "_output_mask.png")).convert("L"))
+              for n in names]
+    masks = [(f"960x540 {n}", m) for n, m in zip(names, sample)]
+    big = [tuple(int(v) for v in s.split("x")) for s in sizes if s != "sample"]
+    masks += [(f"{h}x{w} {names[0]} enlarged", np.ascontiguousarray(resize_nearest(sample[0], h, w))) for h, w in big]
+    for name, m in masks:
+        dm = torch.from_numpy(m.copy()).to("cuda:0")
+        out = ops.mask_largest_contour(dm)
+        for _ in range(3):
+            ops.mask_largest_contour(dm, out)
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(max(reps, 10)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            ops.mask_largest_contour(dm, out)
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        box = decode_contour_box(out.cpu().numpy().tobytes())
+        tracer_ms, ref = _median_ms(lambda: largest_external_contour(m), reps)
+        rec = {"mask": name, "device_ms": round(float(np.median(ts)), 4), "device_min_ms": round(float(min(ts)), 4),
+               "tracer_ms": round(tracer_ms, 2)}
+        if m.size >= 1080 * 1920:
+            rec["filled_ms"] = round(_median_ms(lambda: largest_external_contour_filled(m), reps)[0], 2)
+        rec["tracer_over_device"] = round(tracer_ms / float(np.median(ts)), 1)
+        rec["box"] = box
+        rec["same_as_tracer"] = bool(box == ref)
+        print(json.dumps(rec), flush=True)
+
+    print("# predict_masks end to end, ms per image (host clock): masks only | masks and boxes", flush=True)
+    rng = np.random.default_rng(5)
+    model = UNetModel((H, W, 3), 1, dropout_rate=0.2, device="cuda:0")
+    model.engine.graph_predict = True
+    sources = {"960x540": [np.asarray(Image.open(os.path.join(SAMPLES, n + ".png")).convert("RGB")) for n in names]}
+    for h, w in big:
+        sources[f"{h}x{w}"] = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8)]
+    for size, src in sources.items():
+        for n in batches:
+            images = [src[i % len(src)] for i in range(n)]
+            run = {False: (lambda: model.predict_masks(images, threshold=THR, batch_size=n, bgr=True)),
+                   True: (lambda: model.predict_masks(images, threshold=THR, batch_size=n, bgr=True,
+                                                      return_boxes=True))}
+            for _ in range(2):
+                run[False]()
+                got_masks, got_boxes = run[True]()
+            t = {False: [], True: []}
+            for _ in range(reps):
+                for k in (False, True):
+                    t[k].append(_clock(run[k])[0])
+            k = len(src)
+            # the network has random weights: its masks can hold thousands of components, which the tracer
+            # walks one by one, so it is timed on the 960x540 masks only
+            tracer_ms = (_median_ms(lambda: [largest_external_contour(a) for a in got_masks[:k]], reps)[0]
+                         if got_masks[0].size < 1080 * 1920 else None)
+            filled_ms, ref = _median_ms(lambda: [largest_external_contour_filled(a) for a in got_masks[:k]], reps)
+            same = got_boxes[:k] == ref
+            plain, boxed = (1e3 * float(np.median(t[k_])) / n for k_ in (False, True))
+            print(json.dumps({"size": size, "batch": n, "masks_ms": round(plain, 3), "masks_boxes_ms": round(boxed, 3),
+                              "boxes_cost_ms": round(boxed - plain, 3),
+                              "host_tracer_ms": None if tracer_ms is None else round(tracer_ms / k, 2),
+                              "host_filled_ms": round(filled_ms / k, 2), "same_boxes": bool(same)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only-contour", action="store_true")
+    ap.add_argument("--contour", action="store_true",
+                    help="the device contour section (profiles/contour_predict.txt) instead of the resize rows")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", default="sample,1080x1920,3000x4000")
     ap.add_argument("--batches", default="1,32")
     args = ap.parse_args()
     if args.only_contour:
         return contour_remainder(args.reps)
+    if args.contour:
+        return contour_section(args.reps, args.sizes.split(","), [int(b) for b in args.batches.split(",")])
     assert torch.cuda.is_available(), "bench_imageproc needs the MI355X"
     from PIL import Image
     rng = np.random.default_rng(5)

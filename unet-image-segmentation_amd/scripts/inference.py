@@ -16,6 +16,10 @@ crop (tests/test_imageproc.py).  This post-processing is off the GPU path (SURVE
 on the device instead (model.predict_masks: unet_amd/pipeline.py), bitwise the same arithmetic,
 so the mask and the crop are byte-identical to the default path's; the contour and the crop stay
 on the host.
+
+--device_contour (another extra, off by default, implies --device_imageproc) also finds the largest
+contour's bounding box on the device (predict_masks(..., return_boxes=True)): the host tracer is
+skipped, the lines printed and the files written are the same.
 """
 import argparse
 import os
@@ -48,6 +52,8 @@ def parse_args(argv=None) -> argparse.Namespace:
                         help=f"Minimum contour area threshold for cropping (default: {MIN_CONTOUR_AREA}).")
     parser.add_argument("--device_imageproc", action="store_true",
                         help="Resize the image and the probability map on the GPU (same result, less host time).")
+    parser.add_argument("--device_contour", action="store_true",
+                        help="Also find the crop rectangle on the GPU (implies --device_imageproc; same result).")
     return parser.parse_args(argv)
 
 
@@ -84,14 +90,15 @@ def postprocess_and_save_results(prob, original_bgr, orig_h, orig_w, out_mask, o
     save_mask_and_crop(binary, original_bgr, out_mask, out_crop, min_area)
 
 
-def save_mask_and_crop(binary, original_bgr, out_mask, out_crop, min_area=100.0):
+def save_mask_and_crop(binary, original_bgr, out_mask, out_crop, min_area=100.0, find=largest_external_contour):
+    """find(binary) -> None or (area, (x, y, w, h)): the host tracer, or the device's answer."""
     from PIL import Image
     print(f"Saving binary mask to {out_mask} ...")
     if os.path.dirname(out_mask):
         os.makedirs(os.path.dirname(out_mask), exist_ok=True)
     Image.fromarray(binary).save(out_mask)
     print("Finding largest contour for cropping...")
-    best = largest_external_contour(binary)
+    best = find(binary)
     if best is None:
         print("No contours found in the binary mask. Cropped image not saved.")
         return
@@ -109,7 +116,8 @@ def save_mask_and_crop(binary, original_bgr, out_mask, out_crop, min_area=100.0)
 
 def run_on_device(model, args):
     """--device_imageproc: the decoded RGB image goes to the device as it is; scaling, both resizes
-    and the threshold run there (predict_masks reverses the channels: the network is fed BGR)."""
+    and the threshold run there (predict_masks reverses the channels: the network is fed BGR).
+    --device_contour: the crop rectangle comes back with the mask."""
     from PIL import Image
     print(f"Loading image: {args.input} ...")
     try:
@@ -119,13 +127,17 @@ def run_on_device(model, args):
         sys.exit(1)
     print("Running prediction...")
     try:
-        binary = model.predict_masks([rgb], threshold=args.threshold, bgr=True)[0]
+        if args.device_contour:
+            masks, boxes = model.predict_masks([rgb], threshold=args.threshold, bgr=True, return_boxes=True)
+            binary, find = masks[0], (lambda _mask: boxes[0])
+        else:
+            binary, find = model.predict_masks([rgb], threshold=args.threshold, bgr=True)[0], largest_external_contour
     except Exception as e:
         print(f"Error during model prediction: {e}")
         sys.exit(1)
     print("Postprocessing results...")
     print("Processing predicted mask...")
-    save_mask_and_crop(binary, rgb[..., ::-1], args.output_mask, args.output_cropped, args.min_area)
+    save_mask_and_crop(binary, rgb[..., ::-1], args.output_mask, args.output_cropped, args.min_area, find)
 
 
 def main(argv=None):
@@ -154,7 +166,7 @@ def main(argv=None):
         print("\n--- Error loading model ---")
         print(f"{e}")
         sys.exit(1)
-    if args.device_imageproc:
+    if args.device_imageproc or args.device_contour:
         run_on_device(model, args)
         print("Inference script finished.")
         return

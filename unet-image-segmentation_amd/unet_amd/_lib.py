@@ -12,7 +12,7 @@ from pathlib import Path
 
 LIB_NAME = "libunet_hip.so"
 LIB_PATH = Path(os.environ.get("UNET_HIP_LIB", Path(__file__).with_name(LIB_NAME)))
-ABI_VERSION = 15
+ABI_VERSION = 16
 SPLIT_MAX_SEGS = 64  # UNET_SPLIT_MAX_SEGS
 
 VIEW_PLAIN, VIEW_BNRELU, VIEW_POOL_BNRELU, VIEW_CONCAT = 0, 1, 2, 3
@@ -68,6 +68,20 @@ class UnetI8View(ctypes.Structure):
         ("reserved0", c_int32),
         ("src0", c_void_p),
         ("src1", c_void_p),
+    ]
+
+
+class UnetContourBox(ctypes.Structure):
+    """Mirror of `unet_contour_box` (include/unet_hip.h): 32 bytes."""
+
+    _fields_ = [
+        ("count", c_int32),
+        ("x", c_int32),
+        ("y", c_int32),
+        ("w", c_int32),
+        ("h", c_int32),
+        ("first", c_int32),
+        ("area2", c_int64),
     ]
 
 
@@ -162,6 +176,8 @@ SIGNATURES = {
     "unet_i8_head": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
     "unet_image_resize_u8": (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_int, c_int, P, P]),
     "unet_mask_resize": (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_int, c_float, P, P]),
+    "unet_mask_largest_contour_workspace": (c_size_t, [c_int, c_int]),
+    "unet_mask_largest_contour": (c_int, [P, c_int, c_int, P, P, c_size_t, P]),
 }
 
 _lib = None

@@ -221,3 +221,57 @@ def largest_external_contour(binary: np.ndarray):
         if best is None or a > best[0]:
             best = (a, bounding_rect(c))
     return best
+
+
+def external_contour_stats_filled(binary: np.ndarray) -> List[Tuple[int, Tuple[int, int, int, int], int]]:
+    """(area2, (x, y, w, h), first) of every contour external_contours returns, in its order,
+    without tracing one: area2 is twice cv2.contourArea (an integer), first the linear index
+    y * W + x of the contour's first pixel in raster order.  The closed form the device kernels
+    (csrc/contour.hip) implement:
+
+      O  the background that reaches the frame through background 4-neighbours (the image outside
+         its frame is background); F, the filled image, is everything else: the foreground, its
+         holes and whatever lies inside a hole;
+      the 8-connected components of F are the external contours, ordered by first raster pixel;
+      boundingRect is the component's bounding box; area2 is the sum over the 2x2 pixel cells
+      inside the image of 2 [all four pixels in F] + [exactly three in F] (a cell with three or
+      more F pixels lies in one component): the shoelace area of the chain of boundary pixel
+      centres, counted cell by cell."""
+    from scipy import ndimage
+    fg = np.asarray(binary) != 0
+    H, W = fg.shape
+    pad = np.zeros((H + 2, W + 2), bool)
+    pad[1:-1, 1:-1] = fg
+    bg, _ = ndimage.label(~pad, structure=ndimage.generate_binary_structure(2, 1))
+    filled = (bg != bg[0, 0])[1:-1, 1:-1]
+    lab, n = ndimage.label(filled, structure=np.ones((3, 3), bool))
+    if n == 0:
+        return []
+    flat = lab.ravel()
+    order = np.flatnonzero(flat)
+    labels, where = np.unique(flat[order], return_index=True)
+    first = np.zeros(n + 1, np.int64)
+    first[labels] = order[where]
+    f = filled.astype(np.int64)
+    cells = f[:-1, :-1] + f[:-1, 1:] + f[1:, :-1] + f[1:, 1:]
+    contrib = 2 * (cells == 4) + (cells == 3)
+    cell_lab = np.maximum(np.maximum(lab[:-1, :-1], lab[:-1, 1:]), np.maximum(lab[1:, :-1], lab[1:, 1:]))
+    # (float64 weights: the sums stay far below 2^53, so they are exact)
+    area2 = np.bincount(cell_lab.ravel(), weights=contrib.ravel(), minlength=n + 1).astype(np.int64)
+    boxes = ndimage.find_objects(lab)
+    out = []
+    for lbl in sorted(range(1, n + 1), key=lambda l: first[l]):
+        ys, xs = boxes[lbl - 1]
+        out.append((int(area2[lbl]), (int(xs.start), int(ys.start), int(xs.stop - xs.start), int(ys.stop - ys.start)),
+                    int(first[lbl])))
+    return out
+
+
+def largest_external_contour_filled(binary: np.ndarray):
+    """largest_external_contour(binary), exactly, from external_contour_stats_filled: the largest
+    area2, on ties the first in raster order.  The fast host oracle for large masks."""
+    best = None
+    for area2, rect, _ in external_contour_stats_filled(binary):
+        if best is None or area2 > best[0]:
+            best = (area2, rect)
+    return None if best is None else (best[0] / 2.0, best[1])

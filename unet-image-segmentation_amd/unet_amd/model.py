@@ -164,11 +164,12 @@ class UNetModel:
         return out.cpu().numpy() if is_np else out
 
     def predict_masks(self, images, threshold: float = 0.5, batch_size: int = 32, bgr: bool = True,
-                      return_probs: bool = False):
+                      return_probs: bool = False, return_boxes: bool = False):
         """uint8 images as decoded, of any sizes -> uint8 masks at the images' sizes, the resizes on
-        the device (unet_amd.pipeline.predict_masks)."""
+        the device; return_boxes=True adds each mask's largest-contour crop rectangle, found on the
+        device too (unet_amd.pipeline.predict_masks)."""
         from .pipeline import predict_masks
-        return predict_masks(self, images, threshold, batch_size, bgr, return_probs)
+        return predict_masks(self, images, threshold, batch_size, bgr, return_probs, return_boxes)
 
     def freeze(self, dtype: str = "float16", calibration=None, batch_size=None):
         """A frozen inference copy (unet_amd.frozen.FrozenUNet): BatchNorm folded into the

@@ -1049,3 +1049,38 @@ def mask_resize(prob: Tensor, ytab: Tensor, xtab: Tensor, out: Tensor, threshold
     _call("unet_mask_resize", (9.0 * px * ncls, 1.0 * px + 4.0 * h * w * ncls), _ptr(prob), h, w, ncls, _ptr(ytab),
           _ptr(xtab), oh, ow, float(threshold), _ptr(out), _stream())
     return out
+
+
+CONTOUR_BOX_BYTES = ctypes.sizeof(L.UnetContourBox)
+
+
+def mask_largest_contour(mask: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """uint8 device mask (h, w), dense (a view into a flat buffer at any byte offset will do) ->
+    the 32-byte `unet_contour_box` record of its largest external contour as a uint8 device tensor
+    (32,): `out` (8-byte aligned, filled) or a new one.  Foreground is mask != 0.  The record
+    equals imageproc.largest_external_contour(mask) field by field (pipeline.decode_contour_box
+    gives that form); the workspace comes from the per-stream scratch buffer."""
+    for t, name in ((mask, "mask"),) + (((out, "out"),) if out is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected a torch.Tensor")
+        if not t.is_cuda:
+            raise ValueError(f"{name}: must be a device (HIP) tensor; there is no CPU path")
+        if t.dtype != torch.uint8:
+            raise ValueError(f"{name}: expected torch.uint8, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: must be contiguous")
+    if mask.dim() != 2:
+        raise ValueError(f"mask: expected (h, w), got {tuple(mask.shape)}")
+    h, w = (int(v) for v in mask.shape)
+    if min(h, w) < 1:
+        raise ValueError(f"empty mask {h}x{w}")
+    if h * w > 1 << 30:
+        raise ValueError(f"mask {h}x{w}: more than 2^30 pixels")
+    if out is None:
+        out = torch.empty(CONTOUR_BOX_BYTES, dtype=torch.uint8, device=mask.device)
+    elif out.numel() != CONTOUR_BOX_BYTES or out.data_ptr() % 8:
+        raise ValueError(f"out: expected {CONTOUR_BOX_BYTES} uint8 at an 8-byte aligned address")
+    ws, ws_bytes = _ws(L.query("unet_mask_largest_contour_workspace", h, w), mask.device)
+    px = h * w
+    _call("unet_mask_largest_contour", (0.0, 30.0 * px), _ptr(mask), h, w, _ptr(out), ws, ws_bytes, _stream())
+    return out

@@ -12,6 +12,12 @@ functions, so that a caller hands over images as decoded and gets masks at the i
 Per chunk of images: one upload from pinned memory, one resize launch per image into one batch
 tensor, one model.predict, one mask launch per image, one copy back, one synchronisation.
 Everything is issued on the current stream.
+
+    masks, boxes = model.predict_masks(images, return_boxes=True)
+
+also runs the last step of scripts/inference.py on the device (ops.mask_largest_contour, after each
+image's mask launch): boxes[i] is imageproc.largest_external_contour(masks[i]), the crop rectangle.
+The 32-byte records ride in the chunk's one copy back.
 """
 from __future__ import annotations
 
@@ -149,8 +155,18 @@ def preprocess_images(images: Sequence, input_size, device, bgr: bool = True):
     return x
 
 
+def decode_contour_box(record):
+    """32 bytes of a `unet_contour_box` (any buffer) -> what imageproc.largest_external_contour
+    returns: None, or (area, (x, y, w, h)) with a float area and Python ints."""
+    from ._lib import UnetContourBox
+    b = UnetContourBox.from_buffer_copy(bytes(record))
+    if b.count == 0:
+        return None
+    return b.area2 / 2.0, (int(b.x), int(b.y), int(b.w), int(b.h))
+
+
 def predict_masks(model, images: Sequence, threshold: float = 0.5, batch_size: int = 32, bgr: bool = True,
-                  return_probs: bool = False):
+                  return_probs: bool = False, return_boxes: bool = False):
     """uint8 images (h_i, w_i, c) of any, differing sizes -> a list of uint8 masks (h_i, w_i), each
     at its image's size: 255 where the probability, resized back bilinearly, is > threshold (one
     class), or the argmax class index (several classes; threshold is then unused).
@@ -158,8 +174,12 @@ def predict_masks(model, images: Sequence, threshold: float = 0.5, batch_size: i
     model: a UNetModel, FrozenUNet or FrozenUNetI8.  images: NumPy arrays or device tensors.  bgr: see
     preprocess_images.  return_probs=True returns (masks, probs, inputs): the device probabilities
     (N, H, W, classes) the masks were made from and the device tensor (N, H, W, c) the network was
-    fed.  ValueError, before the device is touched, for a non-uint8 image, a channel count other
-    than the model's, an empty image and a threshold outside (0, 1)."""
+    fed.  return_boxes=True appends boxes as the last element, (masks, boxes) or (masks, probs,
+    inputs, boxes): boxes[i] is None (no foreground) or (area, (x, y, w, h)), the largest external
+    contour of masks[i] found on the device, == imageproc.largest_external_contour(masks[i]);
+    foreground is mask != 0, also for class-index masks.  ValueError, before the device is touched,
+    for a non-uint8 image, a channel count other than the model's, an empty image and a threshold
+    outside (0, 1)."""
     h, w, c, ncls, device = model_geometry(model)
     if not 0.0 < float(threshold) < 1.0:
         raise ValueError(f"threshold must be inside (0, 1), got {threshold}")
@@ -172,19 +192,24 @@ def predict_masks(model, images: Sequence, threshold: float = 0.5, batch_size: i
     from . import ops
     device = torch.device(device)
     masks: List[np.ndarray] = []
-    probs, inputs = [], []
+    probs, inputs, boxes = [], [], []
+    rec = ops.CONTOUR_BOX_BYTES
     with torch.cuda.device(device):
         for lo, hi in _chunks(images, int(batch_size)):
             chunk = images[lo:hi]
             x = preprocess_images(chunk, (h, w, c), device, bgr)
             prob = model.predict(x, batch_size=len(chunk))
             sizes = [(int(a.shape[0]), int(a.shape[1])) for a in chunk]
-            total = sum(a * b for a, b in sizes)
+            npx = sum(a * b for a, b in sizes)
+            box0 = -(-npx // rec) * rec  # the records follow the masks, aligned to their size
+            total = box0 + rec * len(sizes) if return_boxes else npx
             dev = torch.empty(total, dtype=torch.uint8, device=device)
             off = 0
             for i, (ih, iw) in enumerate(sizes):
-                ops.mask_resize(prob[i], coord_table(ih, h, device), coord_table(iw, w, device),
-                                dev[off:off + ih * iw].view(ih, iw), threshold)
+                m = dev[off:off + ih * iw].view(ih, iw)
+                ops.mask_resize(prob[i], coord_table(ih, h, device), coord_table(iw, w, device), m, threshold)
+                if return_boxes:
+                    ops.mask_largest_contour(m, dev[box0 + rec * i:box0 + rec * (i + 1)])
                 off += ih * iw
             stage = _pinned("out", total, device)
             stage[:total].copy_(dev, non_blocking=True)
@@ -194,11 +219,14 @@ def predict_masks(model, images: Sequence, threshold: float = 0.5, batch_size: i
             for ih, iw in sizes:
                 masks.append(flat[off:off + ih * iw].reshape(ih, iw).copy())
                 off += ih * iw
+            if return_boxes:
+                boxes.extend(decode_contour_box(flat[box0 + rec * i:box0 + rec * (i + 1)]) for i in range(len(sizes)))
             if return_probs:
                 probs.append(prob)
                 inputs.append(x)
     if return_probs:
         cat = (lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts, 0))
         empty = (lambda k: torch.empty((0, h, w, k), dtype=torch.float32, device=device))
-        return masks, (cat(probs) if probs else empty(ncls)), (cat(inputs) if inputs else empty(c))
-    return masks
+        out = masks, (cat(probs) if probs else empty(ncls)), (cat(inputs) if inputs else empty(c))
+        return out + (boxes,) if return_boxes else out
+    return (masks, boxes) if return_boxes else masks
