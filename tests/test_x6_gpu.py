@@ -39,7 +39,7 @@ def _planes(ops, w2d: np.ndarray, keep: bool):
 
 def _tiles(m: int, n: int) -> int:
     """128 x 128 tiles of an (m, n) output: the split-precision route needs >= 256 of them and n > 64
-    (gemm.hip rows_x6)"""
+    (gemm_plan.h rows_x6)"""
     return 0 if n <= 64 else (m + 127) // 128 * ((n + 127) // 128)
 
 
@@ -197,8 +197,8 @@ def test_convt_bwd_data_bnstats_x3(ops, drop, n, h, w, cin, cout):
 
 @pytest.mark.parametrize("m,cin,cout", [(33000, 128, 128), (65536, 256, 512), (4100, 96, 200), (1000, 64, 128)])
 def test_pointwise_bwd_filter_fp32_route(ops, m, cin, cout):
-    """Pointwise weight gradient dW = y^T dz on the fp32-MFMA weight-gradient route, the product
-    library's only one (the split-precision form is a lab variant): 128 x 128 and 64-wide output
+    """Pointwise weight gradient dW = y^T dz on the fp32-MFMA weight-gradient route, the only one
+    (weight gradients have no split-precision form): 128 x 128 and 64-wide output
     tiles, ragged pixel counts and column tiles, within TOL of float64."""
     rng = np.random.default_rng(m + cin + cout)
     y = f32(rng.standard_normal((m, cin)))

@@ -1,8 +1,9 @@
 // Timing lab for the rows GEMM (pointwise fwd / BN-backward dgrad shapes of the U-Net at
-// batch 16, 256x256).  Includes the product gemm.hip so its kernels can be instantiated with
-// other tile parameters; candidate kernels are added below.  Prints us and TF/s per variant,
-// and max |diff| against the product kernel's output.
-#include "gemm.hip"
+// batch 16, 256x256).  Includes the product gemm_rows.hip and gemm_wgrad.hip so their kernels can be
+// instantiated with other tile parameters; candidate kernels are added below.  Prints us and TF/s
+// per variant, and max |diff| against the product kernel's output.
+#include "gemm_rows.hip"
+#include "gemm_wgrad.hip"
 #include <vector>
 #include <algorithm>
 #include <cmath>

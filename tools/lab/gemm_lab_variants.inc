@@ -41,7 +41,7 @@ static void run_bnbwd(RowsArgs a, float* C0, float* C1, double fl, size_t n) {
         CK(hipDeviceSynchronize());
         VAR("product", a.C = C1; launch_rows<A_BNBWD, D, E_STORE>(a, 0, "x"));
         if (getenv("LAB_STAMPS")) {
-            const RowsCfg c = rows_cfg(a, A_BNBWD);
+            const RowsCfg c = rows_cfg(A_BNBWD, a.M, a.K, a.N);
             RowsArgs b = a; b.C = C1; b.ko = 0x20000;
             for (int rep = 0; rep < 3; ++rep) {
                 if (c.bn == 256) launch_rows_tile<256, 16, A_BNBWD, D, E_STORE>(b, 0);
@@ -66,7 +66,7 @@ static void run_bnbwd(RowsArgs a, float* C0, float* C1, double fl, size_t n) {
 }
 
 static void run_variants(int mode, RowsArgs a, float* C0, float* C1, double fl, size_t n) {
-    const RowsCfg c = rows_cfg(a, mode == 0 ? A_PLAIN : A_BNBWD);
+    const RowsCfg c = rows_cfg(mode == 0 ? A_PLAIN : A_BNBWD, a.M, a.K, a.N);
     printf("  [product cfg %dx%d]\n", c.bn, c.bk);
     if (mode == 0) {
         a.C = C0; launch_rows<A_PLAIN, false, E_STATS>(a, 0, "x");

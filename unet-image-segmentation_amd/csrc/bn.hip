@@ -384,7 +384,7 @@ __global__ void bn_bwd_store_kernel(const float* sums, int C, int use_bn, float*
     if (use_bn && dgamma) dgamma[c] = sums[C + c];
 }
 
-// dbeta = S1, dgamma = S2 and the dz coefficients of A_BNBWD loads (gemm.hip):
+// dbeta = S1, dgamma = S2 and the dz coefficients of A_BNBWD loads (gemm_rows.hip; common.h bn_bwd_dz4):
 // coef = (mu, p, q) with p = S1 / M, q = rstd * S2 / M (zeros without BatchNorm: dz = g).
 __global__ void bn_bwd_coef_kernel(const float* sums, int C, int64_t M, int use_bn, const float* mean,
                                    const float* rstd, float* dgamma, float* dbeta, float* coef) {

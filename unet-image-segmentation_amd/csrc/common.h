@@ -128,6 +128,27 @@ __device__ __forceinline__ float4 relu4(float4 v) {
 // BatchNorm affine + ReLU as tf.nn.batch_normalization folds it: x*inv + (beta - mean*inv)
 __device__ __forceinline__ float bnrelu(float x, float sc, float sh) { return relu(fmaf(x, sc, sh)); }
 __device__ __forceinline__ float4 bnrelu4(float4 x, float4 sc, float4 sh) { return relu4(fma4(x, sc, sh)); }
+// The BatchNorm + ReLU backward operand of four channels: g = da (dropout already applied where the
+// block has one) masked by the ReLU, then dz = sc * (g - p - (z - mu) * q) with the per-channel
+// (mu, p, q) of bn.hip's finish.  The one definition every kernel that forms dz on the fly uses.
+// In place (g in, dz out).  The statements live in a macro so that gemm_rows_vec, whose generated
+// code changes when they arrive through an inlined function, can take them as text; every other
+// kernel calls bn_bwd_dz4.
+#define UNET_BN_BWD_DZ4(g_, z_, sc_, sh_, mu_, p_, q_)                             \
+    do {                                                                           \
+        g_.x = fmaf(z_.x, sc_.x, sh_.x) > 0.f ? g_.x : 0.f;                        \
+        g_.y = fmaf(z_.y, sc_.y, sh_.y) > 0.f ? g_.y : 0.f;                        \
+        g_.z = fmaf(z_.z, sc_.z, sh_.z) > 0.f ? g_.z : 0.f;                        \
+        g_.w = fmaf(z_.w, sc_.w, sh_.w) > 0.f ? g_.w : 0.f;                        \
+        g_.x = sc_.x * (g_.x - p_.x - (z_.x - mu_.x) * q_.x);                      \
+        g_.y = sc_.y * (g_.y - p_.y - (z_.y - mu_.y) * q_.y);                      \
+        g_.z = sc_.z * (g_.z - p_.z - (z_.z - mu_.z) * q_.z);                      \
+        g_.w = sc_.w * (g_.w - p_.w - (z_.w - mu_.w) * q_.w);                      \
+    } while (0)
+__device__ __forceinline__ void bn_bwd_dz4(float4& g, const float4& z, const float4& sc, const float4& sh,
+                                           const float4& mu, const float4& p, const float4& q) {
+    UNET_BN_BWD_DZ4(g, z, sc, sh, mu, p, q);
+}
 
 // --------------------------------------------------------------- dropout ----
 // Counter-based Bernoulli draw for the logical linear NHWC index i of an element: one splitmix64

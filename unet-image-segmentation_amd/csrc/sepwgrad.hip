@@ -40,7 +40,7 @@ struct SwArgs {
     int ncig;         // ci groups of 64 channels
     // fused block backward (sepconv_bwd_fused_kernel: the whole backward of a 64-output conv block
     // but its depthwise data gradient): dz is formed per tile from the block's incoming gradient da
-    // and raw z exactly as the BN-backward data-gradient GEMM forms it (gemm.hip A_BNBWD), dy =
+    // and raw z exactly as the BN-backward data-gradient GEMM forms it (gemm_rows.hip A_BNBWD), dy =
     // dz . pk^T is computed there and written out (dy_out), and never goes through HBM as dz
     const float *da, *z, *coef, *bsc, *bsh, *pk;
     const float *da_dl, *da_k;  // rank-one da = da_dl[px] * da_k[c] (the binary head), da NULL
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(fb::NT, 2) void sepconv_bwd_fused_kernel(SwArgs g) 
         }
     };
     auto store = [&]() {
-        // dz = sc (g - p - (z - mu) q), g = da [z sc + sh > 0] (as gemm.hip A_BNBWD); this thread's
+        // dz = sc (g - p - (z - mu) q), g = da [z sc + sh > 0] (common.h bn_bwd_dz4); this thread's
         // output-channel quad is cq in every k (BN constants re-read: L1 hits)
         const float4 fsc = ld4(g.bsc + 4 * cq), fsh = ld4(g.bsh + 4 * cq);
         const float4 fmu = ld4(g.coef + 4 * cq), fp = ld4(g.coef + CO + 4 * cq), fq = ld4(g.coef + 2 * CO + 4 * cq);
@@ -173,15 +173,7 @@ __global__ __launch_bounds__(fb::NT, 2) void sepconv_bwd_fused_kernel(SwArgs g) 
         for (int k = 0; k < DQ; ++k) {
             float4 v = rz[k];
             if constexpr (DA1) v = mul4(fk, f4(rz[k].x));  // the product unet_head_bwd would have stored
-            const float4 zz = rzz[k];
-            v.x = fmaf(zz.x, fsc.x, fsh.x) > 0.f ? v.x : 0.f;
-            v.y = fmaf(zz.y, fsc.y, fsh.y) > 0.f ? v.y : 0.f;
-            v.z = fmaf(zz.z, fsc.z, fsh.z) > 0.f ? v.z : 0.f;
-            v.w = fmaf(zz.w, fsc.w, fsh.w) > 0.f ? v.w : 0.f;
-            v.x = fsc.x * (v.x - fp.x - (zz.x - fmu.x) * fq.x);
-            v.y = fsc.y * (v.y - fp.y - (zz.y - fmu.y) * fq.y);
-            v.z = fsc.z * (v.z - fp.z - (zz.z - fmu.z) * fq.z);
-            v.w = fsc.w * (v.w - fp.w - (zz.w - fmu.w) * fq.w);
+            bn_bwd_dz4(v, rzz[k], fsc, fsh, fmu, fp, fq);
             float* d = &Zs[((tid >> 4) + 16 * k) * ZS + 4 * cq];
             d[0] = v.x;
             d[1] = v.y;

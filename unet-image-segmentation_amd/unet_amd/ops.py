@@ -587,7 +587,7 @@ def pointwise_bwd_data_bnrelu(da: Tensor, z: Tensor, m: int, cin: int, cout: int
     if dz is not None:
         _check(dz, "dz", m * cout)
     # (measurement label only) the library forms dz in a streaming pass and runs the plain GEMM
-    # when either side has >= 1024 channels (gemm.hip, unet_pointwise_bwd_data_bnrelu)
+    # when either side has >= 1024 channels (pointwise.hip, unet_pointwise_bwd_data_bnrelu)
     route = "dz_pass+gemm" if dz is not None and (cin >= 1024 or cout >= 1024) else "gemm_bnbwd"
     work = (2.0 * m * cin * cout, 4.0 * (2 * m * cout + m * cin + cin * cout) + (4.0 * m * cout if dz is not None else 0))
     if pkd is not None:
