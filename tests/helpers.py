@@ -6,6 +6,104 @@ import numpy as np
 from oracle import keras_ops as K
 
 
+class record_launches:
+    """Records every kernel launch that goes through ops._call while the `with` block runs.
+
+    One entry per launch: [entry point, 1 if issued on engine.side else 0, arguments], with integer
+    and float arguments by value, pointers as "P" (non-null) or "0" (null), a unet_view as
+    {"view": [mode, c0, c1, drop_rate, drop_seed, six pointer flags]} and an integer array as a list.
+    The workspaces start empty for the block (their byte counts are launch arguments and would
+    otherwise depend on what ran earlier in the process), so warm up inside it and slice."""
+
+    def __init__(self, engine):
+        self.engine = engine
+        self.trace = []
+
+    def _arg(self, a):
+        import ctypes
+        if a is None:
+            return "0"
+        if isinstance(a, (bool, int, float)):
+            return a
+        if isinstance(a, ctypes.c_void_p):
+            return "P" if a.value else "0"
+        if isinstance(a, ctypes.Array):
+            return [int(v) for v in a]
+        v = getattr(a, "_obj", None)  # ctypes.byref(unet_view)
+        if v is not None:
+            flags = "".join("P" if getattr(v, f) else "0" for f in ("src0", "scale0", "shift0", "src1", "scale1", "shift1"))
+            return {"view": [v.mode, v.c0, v.c1, v.drop_rate, v.drop_seed, flags]}
+        raise TypeError(f"unrecorded launch argument {a!r}")
+
+    def __enter__(self):
+        import torch
+        from unet_amd import ops
+        self._ops, self._call, self._ws = ops, ops._call, ops.WORKSPACE
+        side = self.engine.side.cuda_stream
+
+        def call(name, work, *args, **kw):
+            on_side = int(torch.cuda.current_stream().cuda_stream == side)
+            self.trace.append([name, on_side, [self._arg(a) for a in args]])
+            self._call(name, work, *args, **kw)
+
+        ops._call = call
+        ops.WORKSPACE = ops._Workspace()
+        return self
+
+    def __exit__(self, *exc):
+        self._ops._call = self._call
+        self._ops.WORKSPACE = self._ws
+        return False
+
+
+TRACE_CONFIGS = {  # id -> (input size, classes, BatchNorm, dropout, engine attributes); batch 2 throughout
+    "A": ((128, 128, 3), 1, True, 0.2, {}),
+    "B": ((128, 128, 3), 1, True, 0.2, {"overlap": False}),
+    "C": ((128, 128, 3), 1, True, 0.2, {"fuse_block_bwd": False}),
+    "D": ((128, 128, 3), 1, True, 0.2, {"recompute_y_couts": (64, 128)}),
+    "E": ((128, 128, 3), 1, True, 0.2, {"fuse_sepconv": "never"}),
+    "F": ((128, 128, 3), 1, True, 0.2, {"fuse_bn_stats": False}),
+    "G": ((128, 128, 3), 1, True, 0.2, {"fuse_bn_bwd": False}),
+    "H": ((128, 128, 3), 1, True, 0.2, {"dw_fused_filter": False}),
+    "I": ((128, 128, 3), 1, True, 0.2, {"use_x3": False, "x6_gemm": False}),
+    "J1": ((128, 128, 3), 1, True, 0.2, {"img_fused_dwf": False}),
+    "J2": ((128, 128, 3), 1, True, 0.2, {"img_fused_wgrad": False}),
+    "K": ((128, 128, 3), 1, True, 0.2, {"fuse_min_total": 2048}),
+    "L": ((64, 64, 3), 3, True, 0.0, {}),
+    "M": ((64, 64, 4), 1, False, 0.2, {}),
+    "P": ((128, 128, 3), 1, True, 0.2, {}),  # predict (inference forward, eager) instead of a train step
+}
+TRACE_BATCH = 2
+# every attribute a configuration may set, pinned to its default first: the environment cannot change a trace
+TRACE_DEFAULTS = {"overlap": True, "fuse_block_bwd": True, "recompute_y": True, "recompute_y_couts": (64,),
+                  "fuse_sepconv": "auto", "fuse_bn_stats": True, "fuse_bn_bwd": True, "dw_fused_filter": True,
+                  "use_x3": True, "x6_gemm": True, "img_fused_dwf": True, "img_fused_wgrad": True, "defer_sw": True,
+                  "fuse_min_pixels": 64 * 64, "fuse_min_total": 16 * 1024, "graph_predict": False}
+
+
+def step_trace(cid):
+    """The launch trace of configuration `cid`: one warm-up train step (predict for P), then the
+    recorded second one, on a fresh model."""
+    import torch
+    from unet_amd.model import UNetModel
+    from unet_amd.optim import AdamW
+    size, ncls, bn, drop, attrs = TRACE_CONFIGS[cid]
+    model = UNetModel(size, ncls, dropout_rate=drop, use_batch_norm=bn, device="cuda:0")
+    for k, v in {**TRACE_DEFAULTS, **attrs}.items():
+        setattr(model.engine, k, v)
+    model.compile(AdamW(learning_rate=2e-3, weight_decay=1e-4), "dice_loss")
+    rng = np.random.default_rng(7)
+    x = dev(rng.random((TRACE_BATCH,) + size, dtype=np.float32))
+    y = dev(rng.random((TRACE_BATCH,) + size[:2] + (ncls,)) > 0.6)
+    step = (lambda: model.engine.predict(x)) if cid == "P" else (lambda: model.train_step(x, y))
+    with record_launches(model.engine) as rec:
+        step()
+        first = len(rec.trace)
+        step()
+    torch.cuda.synchronize()
+    return rec.trace[first:]
+
+
 def dev(a):
     import torch
     return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float32))).cuda()

@@ -49,3 +49,26 @@ def test_graph_predict_equals_eager(size, ncls):
     e, g = both(xs[3])
     assert torch.equal(e, g)
     eng.graph_predict = False
+
+
+def test_graph_key_covers_the_routing_attributes():
+    """A routing attribute changed after a capture captures anew: the graph cache is keyed like the
+    step plan (shape + plan.Knobs).  fuse_sepconv="never" moves the 64 x 64 level from the fused
+    launch to the split ones; the graph replay must be bitwise the eager forward under that setting,
+    not the earlier capture's route."""
+    from unet_amd.model import UNetModel
+
+    rng = np.random.default_rng(5)
+    eng = UNetModel((64, 64, 3), 1, dropout_rate=0.2, device="cuda:0").engine
+    x = torch.as_tensor(rng.random((1, 64, 64, 3), dtype=np.float32), device="cuda:0")
+    eng.graph_predict = True
+    g0 = eng.predict(x)
+    assert len(eng._pgraphs) == 1
+    eng.fuse_sepconv = "never"
+    g1 = eng.predict(x)
+    assert len(eng._pgraphs) == 2
+    e1 = eng.forward(x, training=False).clone()
+    assert torch.equal(g1, e1)
+    eng.fuse_sepconv = "auto"
+    assert torch.equal(eng.predict(x), g0) and len(eng._pgraphs) == 2  # the first capture is still there
+    eng.graph_predict = False

@@ -17,13 +17,13 @@ eng = model.engine
 # capture the skip-only part of enc2.b2.da right before bneck backward
 orig = eng._block_bwd
 snap = {}
-def hooked(A, b, view_in, dx0, dx1=None, drop_rate=0.0, drop_seed=0):
+def hooked(A, P, b, *args, **kw):
     if b.name == "bneck_block2":
         snap["enc2_skip"] = A.blocks["enc2_block2"].da.clone()
     if b.name == "enc3_block1":
         snap["enc2_before_pool"] = A.blocks["enc2_block2"].da.clone()
         snap["enc3b1_dy"] = None
-    r = orig(A, b, view_in, dx0, dx1, drop_rate, drop_seed)
+    r = orig(A, P, b, *args, **kw)
     if b.name == "enc3_block1":
         snap["enc2_after_pool"] = A.blocks["enc2_block2"].da.clone()
         snap["dy"] = A.dy[: 2 * 8 * 8 * 128].clone()

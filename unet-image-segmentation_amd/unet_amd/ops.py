@@ -209,19 +209,26 @@ class View:
             t = getattr(self, name)
             if t is not None:
                 _check(t, f"view.{name}")
-        v = UnetView()
-        v.mode = self.mode
-        v.c0 = self.c0
-        v.c1 = self.c1 if self.mode == L.VIEW_CONCAT else 0
+        v = view_fields(self.mode, self.c0, self.c1, self.drop_rate, self.drop_seed)
         v.src0 = self.src0.data_ptr()
         v.scale0 = self.scale0.data_ptr() if self.scale0 is not None else None
         v.shift0 = self.shift0.data_ptr() if self.shift0 is not None else None
         v.src1 = self.src1.data_ptr() if self.src1 is not None else None
         v.scale1 = self.scale1.data_ptr() if self.scale1 is not None else None
         v.shift1 = self.shift1.data_ptr() if self.shift1 is not None else None
-        v.drop_rate = self.drop_rate
-        v.drop_seed = self.drop_seed
         return v
+
+
+def view_fields(mode: int, c0: int, c1: int, drop_rate: float, drop_seed: int) -> UnetView:
+    """A unet_view with its shape fields set and null pointers: all the library's `*_supported` /
+    `*_slabs` queries read (plan.ShapeView puts them to it as it is; View.c_struct adds the sources)."""
+    v = UnetView()
+    v.mode = mode
+    v.c0 = c0
+    v.c1 = c1 if mode == L.VIEW_CONCAT else 0
+    v.drop_rate = drop_rate
+    v.drop_seed = drop_seed
+    return v
 
 
 def view_materialize(x: View, n: int, h: int, w: int, out: Tensor) -> Tensor:
@@ -267,8 +274,9 @@ def dwconv3x3_bwd_data(x: View, n, h, w, dk: Tensor, dy: Tensor, dx0: Tensor, dx
           _ptr(dx1), _stream())
 
 
-def dwconv3x3_bwd_data_bnstats_slabs(x: View, n, h, w) -> int:
-    """Slab count of dwconv3x3_bwd_data_bnstats's BatchNorm partials (0: no fused path)."""
+def dwconv3x3_bwd_data_bnstats_slabs(x, n, h, w) -> int:
+    """Slab count of dwconv3x3_bwd_data_bnstats's BatchNorm partials (0: no fused path).  x (here and
+    in the other `*_slabs` / `*_supported` queries): a View, or a plan.ShapeView -- they read its shape only."""
     vs = x.c_struct()
     return L.query("unet_dwconv3x3_bwd_data_bnstats_slabs", ctypes.byref(vs), n, h, w)
 
@@ -374,7 +382,7 @@ def sepconv_set_schedule(schedule: int) -> int:
     return r
 
 
-def sepconv_supported(x: View, n: int, h: int, w: int, cout: int) -> bool:
+def sepconv_supported(x, n: int, h: int, w: int, cout: int) -> bool:
     vs = x.c_struct()
     return bool(L.load().unet_sepconv_fwd_supported(ctypes.byref(vs), n, h, w, cout))
 
@@ -438,7 +446,7 @@ def pool_select(z: Tensor, n: int, h: int, w: int, c: int, gamma: Optional[Tenso
     _call("unet_pool_select", (0.0, 5.0 * n * h * w * c), _ptr(z), n, h, w, c, _ptr(gamma), _ptr(out), _stream())
 
 
-def sepconv_bwd_filter_supported(x: View, n: int, h: int, w: int, cout: int) -> bool:
+def sepconv_bwd_filter_supported(x, n: int, h: int, w: int, cout: int) -> bool:
     vs = x.c_struct()
     return bool(L.load().unet_sepconv_bwd_filter_supported(ctypes.byref(vs), n, h, w, cout))
 
@@ -678,7 +686,7 @@ def conv_transpose2x2_bwd(x: View, n, h, w, cout, k: Tensor, dout: Tensor, dx: O
           _ptr(dk), _ptr(db), ws, wsb, _stream())
 
 
-def conv_transpose2x2_bwd_data_bnstats_slabs(x: View, n, h, w, cout) -> int:
+def conv_transpose2x2_bwd_data_bnstats_slabs(x, n, h, w, cout) -> int:
     """Slab count of conv_transpose2x2_bwd_data_bnstats's BN partials (0: no such path)."""
     vs = x.c_struct()
     return L.query("unet_conv_transpose2x2_bwd_data_bnstats_slabs", ctypes.byref(vs), n, h, w, cout)
@@ -738,7 +746,7 @@ def head_bwd(x: View, n, h, w, ncls, k: Tensor, prob: Tensor, y_true: Tensor, su
           float(smooth), int(loss_kind), float(loss_scale), _ptr(dx), _ptr(dk), _ptr(db), ws, wsb, _stream())
 
 
-def head_bwd_bnstats_slabs(x: View, n, h, w, ncls) -> int:
+def head_bwd_bnstats_slabs(x, n, h, w, ncls) -> int:
     vs = x.c_struct()
     return L.query("unet_head_bwd_bnstats_slabs", ctypes.byref(vs), n, h, w, ncls)
 
