@@ -18,7 +18,15 @@
  *   - reductions are deterministic (fixed order, no float atomics): the same
  *     inputs give bitwise-identical outputs run to run;
  *   - ops needing scratch take (ws, ws_bytes); query the size with the
- *     matching *_workspace() function.
+ *     matching *_workspace() function.  ws_bytes equal to that answer is
+ *     sufficient, a larger value changes no result, and the workspace's
+ *     contents before the call do not matter;
+ *   - a call writes only inside its outputs, its workspace and the caller-
+ *     sized partials buffers; a call that returns < 0 has written nothing;
+ *   - pointers are at least 4-byte aligned.  Which operands may stop there
+ *     (an element-wise kernel is chosen from the pointer) and which must be
+ *     16-byte aligned (refused with < 0 otherwise) is listed in DESIGN.md
+ *     section 3.1; 16-byte alignment of everything is always accepted.
  */
 #ifndef UNET_HIP_H
 #define UNET_HIP_H

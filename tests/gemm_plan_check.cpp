@@ -220,6 +220,76 @@ static const WgradCase kWgrad[] = {
     {524288, 256, 128, 128, 128, 2, 512, 1024},
 };
 
+// The rows GEMMs the op tests launch (test_ops_gpu.py, test_x6_gpu.py, test_fenced_ops_gpu.py), as
+// (amode, M, K, N, planes handed): pointwise forward (A_PLAIN, K = cin, N = cout), plain data gradient
+// (A_PLAIN, K = cout, N = cin), BatchNorm-backward data gradient (A_BNBWD, K = cout, N = cin; from 1024
+// channels on, the dz pass + the A_PLAIN GEMM), ConvT forward (A_BNRELU / A_PLAIN, K = cin, N = 4 cout)
+// and data gradient (A_UNSHUFFLE, K = 4 cout, N = cin).  Expected values follow from the rules in
+// gemm_plan.h by hand; x6 is what rows_x6 answers with those planes.  Only shapes the vectorised
+// kernel takes (K, N multiples of 4) are listed: the scalar kernel has no tile policy.
+struct OpRowsCase {
+    int amode;
+    long long M;
+    int K, N;
+    bool planes, x6;
+    int bn, bk, bm;
+};
+static const OpRowsCase kOpRows[] = {
+    // test_pointwise_and_bn_stats / test_pointwise_bwd (fp32 only)
+    {A_PLAIN, 256, 64, 64, false, false, 64, 16, 128},
+    {A_PLAIN, 300, 64, 128, false, false, 64, 16, 128},      // 3 tiles: narrow
+    {A_PLAIN, 77, 32, 96, false, false, 64, 16, 128},
+    {A_PLAIN, 512, 256, 512, false, false, 64, 32, 128},     // 16 tiles: narrow, K >= 256
+    {A_PLAIN, 24653, 64, 64, false, false, 64, 16, 128},
+    {A_PLAIN, 24653, 32, 128, false, false, 64, 16, 128},    // 193 tiles: narrow
+    {A_PLAIN, 129, 64, 68, false, false, 64, 16, 128},       // the row x column tails
+    {A_PLAIN, 127, 64, 48, false, false, 64, 16, 128},
+    {A_PLAIN, 1, 64, 4, false, false, 64, 16, 128},
+    {A_PLAIN, 129, 68, 64, false, false, 64, 16, 128},       // their data gradient (K = cout, N = cin)
+    {A_PLAIN, 200, 512, 256, false, false, 64, 32, 128},     // test_pointwise_bwd (200, 256, 512)
+    {A_PLAIN, 64, 1024, 1024, false, false, 64, 32, 128},
+    // test_pointwise_fwd_x3
+    {A_PLAIN, 33000, 96, 160, true, true, 128, 16, 128},     // 258 x 2 tiles
+    {A_PLAIN, 33000, 96, 160, false, false, 128, 16, 128},
+    {A_PLAIN, 16384, 512, 1024, true, true, 128, 32, 128},
+    {A_PLAIN, 4096, 256, 256, true, false, 64, 32, 128},     // 64 tiles: narrow, fp32 route
+    {A_PLAIN, 200, 48, 64, true, false, 64, 16, 128},
+    // test_pointwise_bwd_data_bnrelu(_x3)
+    {A_BNBWD, 300, 32, 16, false, false, 64, 32, 128},
+    {A_BNBWD, 1000, 128, 64, false, false, 64, 32, 128},
+    {A_BNBWD, 257, 64, 128, false, false, 128, 32, 64},      // 3 tiles, N >= 128: 64-row tiles
+    {A_BNBWD, 129, 68, 64, false, false, 64, 32, 128},
+    {A_BNBWD, 33000, 128, 96, true, true, 128, 32, 128},     // 258 tiles
+    {A_BNBWD, 33000, 128, 96, false, false, 128, 32, 128},
+    {A_BNBWD, 16384, 256, 256, true, true, 128, 32, 64},     // 128 x 2 = 256 tiles: still narrow (< 257)
+    {A_BNBWD, 33000, 64, 512, true, true, 256, 16, 128},     // 258 x 2 >= 512
+    {A_BNBWD, 33000, 64, 512, false, false, 256, 16, 128},
+    {A_BNBWD, 33000, 48, 64, true, false, 64, 32, 128},      // K % 32 != 0
+    {A_BNBWD, 4096, 256, 512, true, false, 128, 32, 64},     // 128 tiles
+    {A_BNBWD, 40000, 64, 40, true, false, 64, 32, 128},
+    {A_PLAIN, 33000, 1024, 128, true, true, 128, 32, 128},   // cout 1024: dz pass + plain GEMM
+    {A_PLAIN, 33000, 1024, 128, false, false, 128, 32, 128},
+    {A_PLAIN, 520, 64, 1024, false, false, 64, 16, 128},     // test_ops (520, 1024, 64)
+    // ConvT forward / data gradient (test_conv_transpose, test_conv_transpose_fwd_x3, test_convt_bwd_data_bnstats_x3)
+    {A_BNRELU, 32, 64, 128, false, false, 64, 16, 128},
+    {A_BNRELU, 129, 64, 128, false, false, 64, 16, 128},
+    {A_BNRELU, 33020, 64, 128, true, true, 128, 16, 128},    // (2, 130, 127, 64, 32): 258 tiles
+    {A_BNRELU, 16384, 256, 512, true, true, 128, 32, 128},
+    {A_BNRELU, 17589, 96, 160, true, true, 128, 16, 128},
+    {A_BNRELU, 16, 1024, 2048, true, false, 64, 32, 128},
+    {A_UNSHUFFLE, 129, 128, 64, false, false, 64, 16, 128},
+    {A_UNSHUFFLE, 33020, 128, 64, true, false, 64, 16, 128},
+    {A_UNSHUFFLE, 16384, 512, 256, true, true, 64, 16, 128},   // 256 tiles: narrow
+    {A_UNSHUFFLE, 64, 2048, 1024, true, false, 64, 16, 128},
+};
+
+// convt_bnpart_bm for test_convt_bwd_data_bnstats(_x3): (M, N = cin)
+static const BmCase kOpBm[] = {
+    {128, 128, 64}, {35, 64, 64},  {72, 256, 64},      {512, 128, 64},  {36864, 128, 128},
+    {1, 64, 64},    {127, 64, 64}, {129, 68, 64},      {33020, 64, 128}, {16384, 256, 128},
+    {64, 1024, 64}, {72, 48, 64},
+};
+
 static void check_rows(int amode, long long M, int K, int N, bool x6, int bn, int bk, int bm) {
     const RowsCfg c = rows_cfg(amode, M, K, N);
     const bool ok = rows_x6(amode, M, K, N, true) == x6 && !rows_x6(amode, M, K, N, false) && c.bn == bn &&
@@ -256,6 +326,42 @@ int main() {
                         (long long)w.mslice);
         CHECK(ok);
         CHECK(w.mslice % BK == 0 && (long long)w.S * w.mslice >= e.M);
+    }
+    // the op tests' shapes: each reaches the tile it is listed with, and every value the policy can
+    // return is reached by a case whose M is not a multiple of the 128-row tile
+    {
+        const int kCfgs[][3] = {{64, 16, 128}, {64, 32, 128}, {128, 16, 128}, {128, 32, 128}, {256, 16, 128}, {128, 32, 64}};
+        bool seen[6] = {}, x6_on = false, x6_off = false, bm64 = false, bm128 = false;
+        for (const OpRowsCase& r : kOpRows) {
+            const RowsCfg c = rows_cfg(r.amode, r.M, r.K, r.N);
+            const bool x6 = rows_x6(r.amode, r.M, r.K, r.N, r.planes);
+            const bool ok = x6 == r.x6 && c.bn == r.bn && c.bk == r.bk && c.bm == r.bm;
+            if (!ok)
+                std::printf("op rows amode %d M %lld K %d N %d planes %d: x6 %d cfg {%d, %d, %d}\n", r.amode, r.M, r.K, r.N,
+                            (int)r.planes, (int)x6, c.bn, c.bk, c.bm);
+            CHECK(ok);
+            CHECK(r.K % 4 == 0 && r.N % 4 == 0);
+            if (r.M % 128 == 0) continue;
+            for (int i = 0; i < 6; ++i)
+                // (the split-precision route runs its own 128 x 32 tile whatever rows_cfg says)
+                if (!x6 && c.bn == kCfgs[i][0] && c.bk == kCfgs[i][1] && c.bm == kCfgs[i][2]) seen[i] = true;
+            (x6 ? x6_on : x6_off) = true;
+        }
+        for (int i = 0; i < 6; ++i) {
+            if (!seen[i]) std::printf("no ragged-M op case reaches {%d, %d, bm %d}\n", kCfgs[i][0], kCfgs[i][1], kCfgs[i][2]);
+            CHECK(seen[i]);
+        }
+        CHECK(x6_on && x6_off);
+        for (const BmCase& b : kOpBm) {
+            const int bm = convt_bnpart_bm(b.M, b.N);
+            if (bm != b.bm) std::printf("op convt_bnpart_bm(%lld, %d) = %d, expected %d\n", b.M, b.N, bm, b.bm);
+            CHECK(bm == b.bm);
+            if (b.M % 128) (bm == 64 ? bm64 : bm128) = true;
+        }
+        CHECK(bm64 && bm128);
+        // the weight-gradient slice tail of test_pointwise_bwd (1033, 64, 68): two slices, the last ragged
+        const WgradPlan w = wgrad_plan(1033, 64, 68);
+        CHECK(w.S == 2 && w.mslice == 528 && w.bp == 64 && w.bq == 128 && 1033 - w.mslice < w.mslice);
     }
     if (g_failed) return 1;
     std::printf("gemm_plan_check OK\n");

@@ -8,7 +8,8 @@ Reference: model/u_net.py:14-25 (SeparableConv2D depthwise half -> BatchNormaliz
 import numpy as np
 import pytest
 
-from helpers import bn_affine, dev, f32, host, rel_err
+import fenced
+from helpers import bn_affine, f32, host, rel_err
 from oracle import keras_ops as K
 
 pytestmark = pytest.mark.gpu
@@ -20,6 +21,26 @@ torch = pytest.importorskip("torch")
 def ops():
     from unet_amd import ops as O
     return O
+
+
+mem = None  # the running test's fenced.Arena, set by _fenced
+
+
+@pytest.fixture(autouse=True)
+def _fenced(ops):
+    """Every allocation of a test goes through `mem`; workspaces have exactly the queried size.
+    After the body: no fence byte changed and every `mem.empty` output was written in full."""
+    global mem
+    mem = fenced.Arena("cuda")
+    ws = fenced.FencedWorkspace("cuda")
+    with ws.installed(ops):
+        yield mem
+        mem.check(extra=[ws])
+    mem = None
+
+
+def dev(a):
+    return mem.inp(a)
 
 
 @pytest.mark.parametrize("use_bn", [True, False])
@@ -40,18 +61,18 @@ def test_dwconv_bwd_data_bnstats_dwf(ops, use_bn, n, h, w, c):
     m = n * h * w
     res = {}
     for fused in (True, False):
-        part = torch.zeros(ops.bn_stats_partials_numel(S, c), device="cuda")
-        dx = torch.full((n, h, w, c), 7.0, device="cuda")
+        part = mem.zeros(ops.bn_stats_partials_numel(S, c))
+        dx = mem.full((n, h, w, c), 7.0)
         if fused:
-            slabs = torch.full((S * 9 * c,), 3.0, device="cuda")
+            slabs = mem.full((S * 9 * c,), 3.0)
             ops.dwconv3x3_bwd_data_bnstats_dwf(v, n, h, w, dev(dk), dev(dy), dx, mu, rs, part, slabs)
-            ddk = torch.full((3, 3, c, 1), 5.0, device="cuda")
+            ddk = mem.full((3, 3, c, 1), 5.0)
             ops.reduce_slabs(slabs, S, 9 * c, ddk)
         else:
             ops.dwconv3x3_bwd_data_bnstats(v, n, h, w, dev(dk), dev(dy), dx, mu, rs, part)
-            ddk = torch.full((3, 3, c, 1), 5.0, device="cuda")
+            ddk = mem.full((3, 3, c, 1), 5.0)
             ops.dwconv3x3_bwd_filter(v, n, h, w, dev(dy), ddk)
-        dg, db, coef = torch.zeros(c, device="cuda"), torch.zeros(c, device="cuda"), torch.empty(3 * c, device="cuda")
+        dg, db, coef = mem.zeros(c), mem.zeros(c), mem.empty(3 * c)
         ops.bn_relu_bwd_stats_finish(part, S, m, c, mu, rs, use_bn, dg if use_bn else None, db, coef)
         res[fused] = (host(dx), host(db), host(dg), host(coef), host(ddk))
     for i in range(4):  # dx and the statistics: the same arithmetic in both launches

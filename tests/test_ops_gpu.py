@@ -4,7 +4,8 @@ the 128-row tile, 3-channel inputs, 3-channel outputs) and every activation-view
 import numpy as np
 import pytest
 
-from helpers import bn_affine, dev, f32, host, norm_err, rel_err, view_value
+import fenced
+from helpers import bn_affine, f32, host, norm_err, rel_err, view_value
 from oracle import keras_ops as K
 
 pytestmark = pytest.mark.gpu
@@ -16,6 +17,26 @@ torch = pytest.importorskip("torch")
 def ops():
     from unet_amd import ops as O
     return O
+
+
+mem = None  # the running test's fenced.Arena, set by _fenced
+
+
+@pytest.fixture(autouse=True)
+def _fenced(ops):
+    """Every allocation of a test goes through `mem`; workspaces have exactly the queried size.
+    After the body: no fence byte changed and every `mem.empty` output was written in full."""
+    global mem
+    mem = fenced.Arena("cuda")
+    ws = fenced.FencedWorkspace("cuda")
+    with ws.installed(ops):
+        yield mem
+        mem.check(extra=[ws])
+    mem = None
+
+
+def dev(a):
+    return mem.inp(a)
 
 
 def _mk_view(O, mode, t, drop_rate=0.0, drop_seed=0):
@@ -46,6 +67,11 @@ def _view_inputs(rng, mode, n, h, w, c0, c1=0):
     return a, {k: dev(v) for k, v in a.items()}
 
 
+# Row tails (m: one row, one short of the 128-row tile, one past it) crossed with column tails (cout:
+# below one column tile, not a multiple of 32, one vector past 64), as (m, cin, cout)
+ROW_COL_TAILS = [(m, 64, cout) for m in (1, 127, 129) for cout in (4, 48, 68)]
+ROW_COL_TAILS_OFF = [(m, cin, cout, 0.0) for m, cin, cout in ROW_COL_TAILS]
+
 VIEW_CASES = [
     # mode, n, h, w, c0, c1, drop
     (0, 2, 9, 7, 3, 0, 0.0),      # image input: 3 channels, scalar path, ragged pixels
@@ -55,6 +81,13 @@ VIEW_CASES = [
     (3, 2, 8, 6, 16, 16, 0.0),
     (3, 2, 8, 8, 8, 8, 0.2),      # decoder concat with dropout
     (1, 1, 4, 4, 64, 0, 0.2),
+    # pixel counts 1, 127 and 129: one pixel, one short of a 128-row tile, one past it
+    (0, 1, 1, 1, 8, 0, 0.0),
+    (1, 1, 1, 1, 3, 0, 0.0),
+    (1, 1, 1, 127, 16, 0, 0.0),
+    (2, 1, 1, 127, 8, 0, 0.0),
+    (3, 1, 3, 43, 8, 4, 0.2),
+    (0, 1, 3, 43, 68, 0, 0.0),
 ]
 
 
@@ -63,7 +96,7 @@ def test_view_materialize(ops, mode, n, h, w, c0, c1, drop):
     rng = np.random.default_rng(10 + mode)
     a, t = _view_inputs(rng, mode, n, h, w, c0, c1)
     v = _mk_view(ops, mode, t, drop, 1234)
-    out = torch.empty((n, h, w, c0 + c1), device="cuda")
+    out = mem.empty((n, h, w, c0 + c1))
     ops.view_materialize(v, n, h, w, out)
     ref = view_value(mode, a["src0"], a.get("sc0"), a.get("sh0"), a.get("src1"), a.get("sc1"), a.get("sh1"),
                      drop, 1234)
@@ -77,7 +110,7 @@ def test_dwconv_fwd(ops, mode, n, h, w, c0, c1, drop):
     C = c0 + c1
     dk = f32(rng.standard_normal((3, 3, C, 1)))
     v = _mk_view(ops, mode, t, drop, 99)
-    y = torch.empty((n, h, w, C), device="cuda")
+    y = mem.empty((n, h, w, C))
     ops.dwconv3x3_fwd(v, n, h, w, dev(dk), y)
     xv = view_value(mode, a["src0"], a.get("sc0"), a.get("sh0"), a.get("src1"), a.get("sc1"), a.get("sh1"), drop, 99)
     assert rel_err(host(y), K.depthwise3x3(xv, dk)) < 2e-6
@@ -96,23 +129,23 @@ def test_dwconv_bwd(ops, mode, n, h, w, c0, c1, drop):
     if drop > 0:
         dxv = dxv * K.dropout_mult(7, dxv.shape, drop)
     # filter gradient
-    g = torch.empty((3, 3, C, 1), device="cuda")
+    g = mem.empty((3, 3, C, 1))
     ops.dwconv3x3_bwd_filter(v, n, h, w, dev(dy), g)
     assert rel_err(host(g), ddk) < 1e-5
     # data gradient, routed per view mode
     if mode in (0, 1):
-        dx0 = torch.empty((n, h, w, C), device="cuda")
+        dx0 = mem.empty((n, h, w, C))
         ops.dwconv3x3_bwd_data(v, n, h, w, dev(dk), dev(dy), dx0)
         assert rel_err(host(dx0), dxv) < 2e-6
     elif mode == 3:
-        dx0 = torch.empty((n, h, w, c0), device="cuda")
-        dx1 = torch.empty((n, h, w, c1), device="cuda")
+        dx0 = mem.empty((n, h, w, c0))
+        dx1 = mem.empty((n, h, w, c1))
         ops.dwconv3x3_bwd_data(v, n, h, w, dev(dk), dev(dy), dx0, dx1)
         assert rel_err(host(dx0), dxv[..., :c0]) < 2e-6
         assert rel_err(host(dx1), dxv[..., c0:]) < 2e-6
     else:
         init = f32(rng.standard_normal((n, 2 * h, 2 * w, c0)))
-        dx0 = dev(init)
+        dx0 = mem.inp(init, fence=mem.out_fence)  # the pool route accumulates into dx0
         ops.dwconv3x3_bwd_data(v, n, h, w, dev(dk), dev(dy), dx0)
         act = K.relu(a["src0"] * a["sc0"] + a["sh0"])
         ref = init + K.maxpool2_bwd(act, dxv)
@@ -122,13 +155,13 @@ def test_dwconv_bwd(ops, mode, n, h, w, c0, c1, drop):
 @pytest.mark.parametrize("m,cin,cout,off", [(100, 3, 64, 0.0), (256, 64, 64, 0.0), (300, 64, 128, 0.0),
                                             (128, 128, 256, 0.0), (77, 32, 96, 0.0), (512, 256, 512, 0.0),
                                             # > 64 partials: several finalize chunks; |mean| >> std
-                                            (24653, 64, 64, 0.0), (24653, 32, 128, 25.0)])
+                                            (24653, 64, 64, 0.0), (24653, 32, 128, 25.0)] + ROW_COL_TAILS_OFF)
 def test_pointwise_and_bn_stats(ops, m, cin, cout, off):
     rng = np.random.default_rng(m + cin)
     y = f32(rng.standard_normal((m, cin)) + off)
     pk = f32(rng.standard_normal((1, 1, cin, cout)) / np.sqrt(cin))
-    z = torch.empty((m, cout), device="cuda")
-    part = torch.zeros(ops.bn_partials_numel(m, cout), device="cuda")
+    z = mem.empty((m, cout))
+    part = mem.zeros(ops.bn_partials_numel(m, cout))
     ops.pointwise_fwd(dev(y), m, cin, cout, dev(pk), z, part)
     zr = y @ pk[0, 0]
     assert rel_err(host(z), zr) < 5e-6
@@ -136,7 +169,7 @@ def test_pointwise_and_bn_stats(ops, m, cin, cout, off):
     mm = f32(rng.standard_normal(cout) * 0.1)
     mv = f32(1 + rng.random(cout))
     tm, tv = dev(mm), dev(mv)
-    outs = [torch.empty(cout, device="cuda") for _ in range(4)]
+    outs = [mem.empty(cout) for _ in range(4)]
     ops.bn_finalize(part, m, cout, dev(gamma), dev(beta), 1e-3, 0.99, tm, tv, True, *outs)
     zz = zr[:, None, None, :].reshape(m, 1, 1, cout)
     out, mean, var = K.bn_train(zz, gamma, beta)
@@ -148,12 +181,12 @@ def test_pointwise_and_bn_stats(ops, m, cin, cout, off):
     assert rel_err(host(outs[3]), beta - mean * inv) < 1e-4
     assert rel_err(host(tm), mm2) < 1e-5 and rel_err(host(tv), mv2) < 1e-5
     # again: the finalize's arrival counters were left zero, the result is bitwise the same
-    outs2 = [torch.empty(cout, device="cuda") for _ in range(4)]
+    outs2 = [mem.empty(cout) for _ in range(4)]
     ops.bn_finalize(part, m, cout, dev(gamma), dev(beta), 1e-3, 0.99, None, None, False, *outs2)
     assert all(torch.equal(a, b) for a, b in zip(outs, outs2))
     assert not torch.any(part[-((cout + 63) // 64):].view(torch.int32))
     # no-partials path (inference GEMM epilogue)
-    z2 = torch.empty((m, cout), device="cuda")
+    z2 = mem.empty((m, cout))
     ops.pointwise_fwd(dev(y), m, cin, cout, dev(pk), z2, None)
     assert torch.equal(z, z2)
 
@@ -173,23 +206,23 @@ def test_bn_sync_moments(ops, rows, cout, off):
     mm = f32(rng.standard_normal(cout) * 0.1)
     mv = f32(1 + rng.random(cout))
     R = 1 + 2 * cout
-    recs = torch.empty(len(rows) * R, dtype=torch.float64, device="cuda")
+    recs = mem.empty(len(rows) * R, dtype=torch.float64)
     for i, (r, y) in enumerate(zip(rows, ys)):
-        z = torch.empty((r, cout), device="cuda")
-        part = torch.zeros(ops.bn_partials_numel(r, cout), device="cuda")
+        z = mem.empty((r, cout))
+        part = mem.zeros(ops.bn_partials_numel(r, cout))
         ops.pointwise_fwd(dev(y), r, cin, cout, dev(pk), z, part)
         ops.bn_moments(part, r, cout, recs[i * R:(i + 1) * R])
     tm, tv = dev(mm), dev(mv)
-    outs = [torch.empty(cout, device="cuda") for _ in range(4)]
+    outs = [mem.empty(cout) for _ in range(4)]
     ops.bn_finalize_moments(recs, len(rows), cout, dev(gamma), dev(beta), 1e-3, 0.99, tm, tv, True, *outs)
     # reference: one replica holding every row
     M = sum(rows)
     yall = np.concatenate(ys)
-    zall = torch.empty((M, cout), device="cuda")
-    pall = torch.zeros(ops.bn_partials_numel(M, cout), device="cuda")
+    zall = mem.empty((M, cout))
+    pall = mem.zeros(ops.bn_partials_numel(M, cout))
     ops.pointwise_fwd(dev(yall), M, cin, cout, dev(pk), zall, pall)
     tm2, tv2 = dev(mm), dev(mv)
-    ref = [torch.empty(cout, device="cuda") for _ in range(4)]
+    ref = [mem.empty(cout) for _ in range(4)]
     ops.bn_finalize(pall, M, cout, dev(gamma), dev(beta), 1e-3, 0.99, tm2, tv2, True, *ref)
     for a, b in zip(outs + [tm, tv], ref + [tm2, tv2]):
         assert rel_err(host(a), host(b)) < 2e-6
@@ -199,7 +232,7 @@ def test_bn_sync_moments(ops, rows, cout, off):
     assert rel_err(host(outs[1]), 1 / np.sqrt(var + 1e-3)) < 1e-5
     # backward coefficients from (all-reduced) sums
     sums = dev(f32(rng.standard_normal(2 * cout)))
-    coef = torch.empty(3 * cout, device="cuda")
+    coef = mem.empty(3 * cout)
     ops.bn_bwd_coef(sums, M, cout, True, outs[0], outs[1], coef)
     sh = host(sums)
     want = np.concatenate([host(outs[0]), sh[:cout] / M, host(outs[1]) * (sh[cout:] / M)])
@@ -207,15 +240,17 @@ def test_bn_sync_moments(ops, rows, cout, off):
 
 
 @pytest.mark.parametrize("m,cin,cout", [(100, 3, 64), (256, 64, 64), (300, 128, 64), (200, 256, 512),
-                                        (64, 1024, 1024)])
+                                        (64, 1024, 1024),
+                                        (1033, 64, 68)]  # wgrad_plan: S = 2 slices of 528 rows, the last one ragged
+                         + ROW_COL_TAILS)
 def test_pointwise_bwd(ops, m, cin, cout):
     rng = np.random.default_rng(m * 3 + cout)
     y = f32(rng.standard_normal((m, cin)))
     pk = f32(rng.standard_normal((1, 1, cin, cout)) / np.sqrt(cin))
     dz = f32(rng.standard_normal((m, cout)))
-    dy = torch.empty((m, cin), device="cuda")
+    dy = mem.empty((m, cin))
     ops.pointwise_bwd_data(dev(dz), m, cin, cout, dev(pk), dy)
-    dpk = torch.empty((1, 1, cin, cout), device="cuda")
+    dpk = mem.empty((1, 1, cin, cout))
     ops.pointwise_bwd_filter(dev(y), dev(dz), m, cin, cout, dpk)
     ry, rpk = K.pointwise_bwd(y.reshape(m, 1, 1, cin), pk, dz.reshape(m, 1, 1, cout))
     assert rel_err(host(dy), ry.reshape(m, cin)) < 5e-6
@@ -223,7 +258,7 @@ def test_pointwise_bwd(ops, m, cin, cout):
 
 
 @pytest.mark.parametrize("use_bn,drop", [(True, 0.0), (True, 0.2), (False, 0.0)])
-@pytest.mark.parametrize("m,c", [(300, 16), (1000, 64), (96, 3)])
+@pytest.mark.parametrize("m,c", [(300, 16), (1000, 64), (96, 3)] + [(m, c) for m, _, c in ROW_COL_TAILS])
 def test_bn_relu_bwd(ops, use_bn, drop, m, c):
     rng = np.random.default_rng(m + c)
     z = f32(rng.standard_normal((m, 1, 1, c)) * 2 + 0.3)
@@ -238,9 +273,9 @@ def test_bn_relu_bwd(ops, use_bn, drop, m, c):
         mean = var = rstd = np.zeros(c)
         scale, shift = np.ones(c), beta
     dmult = K.dropout_mult(55, da.shape, drop) if drop > 0 else None
-    dg = torch.zeros(c, device="cuda")
-    db = torch.zeros(c, device="cuda")
-    dz = torch.empty((m, c), device="cuda")
+    dg = mem.zeros(c)
+    db = mem.zeros(c)
+    dz = mem.empty((m, c))
     ops.bn_relu_bwd(dev(da), dev(z), m, c, dev(f32(mean)), dev(f32(rstd)), dev(scale), dev(shift), use_bn, drop, 55,
                     dg if use_bn else None, db, dz)
     if use_bn:
@@ -275,13 +310,13 @@ def test_pointwise_bwd_data_bnrelu_wgrad(ops, use_bn, m, cout):
     else:
         mean = rstd = np.zeros(c)
         scale, shift = f32(np.ones(c)), beta
-    dg, db, coef = torch.zeros(c, device="cuda"), torch.zeros(c, device="cuda"), torch.empty(3 * c, device="cuda")
+    dg, db, coef = mem.zeros(c), mem.zeros(c), mem.empty(3 * c)
     ts, th = dev(scale), dev(shift)
     ops.bn_relu_bwd_stats(dev(da), dev(z), m, c, dev(f32(mean)), dev(f32(rstd)), ts, th, use_bn, 0.0, 0,
                           dg if use_bn else None, db, coef)
-    dy_f, dy_p = torch.empty((m, cin), device="cuda"), torch.empty((m, cin), device="cuda")
-    dpk_f, dpk_p = torch.full((1, 1, cin, cout), 7.0, device="cuda"), torch.empty((1, 1, cin, cout), device="cuda")
-    dz = torch.empty((m, c), device="cuda")
+    dy_f, dy_p = mem.empty((m, cin)), mem.empty((m, cin))
+    dpk_f, dpk_p = mem.full((1, 1, cin, cout), 7.0), mem.empty((1, 1, cin, cout))
+    dz = mem.empty((m, c))
     ops.pointwise_bwd_data_bnrelu_wgrad(dev(da), dev(z), m, cin, cout, dev(pk), ts, th, coef, dev(y), dy_f, dpk_f)
     assert ops.L.query("unet_pointwise_bwd_data_bnrelu_wgrad_workspace", m, cin, 48) == 0
     ops.pointwise_bwd_data_bnrelu(dev(da), dev(z), m, cin, cout, dev(pk), ts, th, coef, 0.0, 0, dy_p, dz)
@@ -314,18 +349,18 @@ def test_image_block_bwd_wgrad(ops, n, h, w, wcin, cout):
     mean, var = z.mean(0), z.var(0)
     rstd = 1 / np.sqrt(var + 1e-3)
     ts, th = dev(f32(gamma * rstd)), dev(f32(beta - mean * gamma * rstd))
-    dg, db, coef = torch.zeros(c, device="cuda"), torch.zeros(c, device="cuda"), torch.empty(3 * c, device="cuda")
+    dg, db, coef = mem.zeros(c), mem.zeros(c), mem.empty(3 * c)
     ops.bn_relu_bwd_stats(dev(da), dev(z), m, c, dev(f32(mean)), dev(f32(rstd)), ts, th, True, 0.0, 0, dg, db, coef)
-    ddk = torch.full((3, 3, wcin, 1), 7.0, device="cuda")
-    dpk = torch.full((1, 1, wcin, cout), 7.0, device="cuda")
+    ddk = mem.full((3, 3, wcin, 1), 7.0)
+    dpk = mem.full((1, 1, wcin, cout), 7.0)
     tx = dev(x)
     ops.image_block_bwd_wgrad(tx, n, h, w, wcin, cout, dev(pk), ts, th, coef, dev(da), dev(z), dev(y), ddk, dpk)
     assert ops.L.query("unet_image_block_bwd_wgrad_workspace", n, h, w, 48) == 0
-    dy = torch.empty((m, cin), device="cuda")
-    dpk_p = torch.empty((1, 1, cin, cout), device="cuda")
+    dy = mem.empty((m, cin))
+    dpk_p = mem.empty((1, 1, cin, cout))
     ops.pointwise_bwd_data_bnrelu_wgrad(dev(da), dev(z), m, cin, cout, dev(pk), ts, th, coef, dev(y), dy, dpk_p)
     assert rel_err(host(dpk), host(dpk_p)[:, :, :wcin]) < 1e-5
-    ddk_p = torch.empty((3, 3, cin, 1), device="cuda")
+    ddk_p = mem.empty((3, 3, cin, 1))
     ops.dwconv3x3_bwd_filter(ops.View.plain(tx), n, h, w, dy, ddk_p)
     assert rel_err(host(ddk), host(ddk_p)[:, :, :wcin]) < 1e-5
     g = host(dy).astype(np.float64).reshape(n, h, w, cin)
@@ -336,7 +371,8 @@ def test_image_block_bwd_wgrad(ops, n, h, w, wcin, cout):
 
 @pytest.mark.parametrize("use_bn,drop", [(True, 0.0), (True, 0.2), (False, 0.0)])
 @pytest.mark.parametrize("m,cin,cout", [(300, 16, 32), (1000, 64, 128), (257, 128, 64), (128, 4, 8),
-                                       (520, 1024, 64)])  # cin >= 1024: dz pass + plain GEMM
+                                       (520, 1024, 64)]  # cin >= 1024: dz pass + plain GEMM
+                         + ROW_COL_TAILS)
 def test_pointwise_bwd_data_bnrelu(ops, use_bn, drop, m, cin, cout):
     """BN + ReLU (+ dropout) backward folded into the pointwise data-gradient GEMM's operand load,
     against the oracle's bn_relu_bwd followed by the pointwise backward."""
@@ -355,14 +391,14 @@ def test_pointwise_bwd_data_bnrelu(ops, use_bn, drop, m, cin, cout):
         mean = var = rstd = np.zeros(c)
         scale, shift = np.ones(c), beta
     dmult = K.dropout_mult(55, da.shape, drop) if drop > 0 else None
-    dg = torch.zeros(c, device="cuda")
-    db = torch.zeros(c, device="cuda")
-    coef = torch.empty(3 * c, device="cuda")
+    dg = mem.zeros(c)
+    db = mem.zeros(c)
+    coef = mem.empty(3 * c)
     ts, th = dev(scale), dev(shift)
     ops.bn_relu_bwd_stats(dev(da), dev(z), m, c, dev(f32(mean)), dev(f32(rstd)), ts, th, use_bn, drop, 55,
                           dg if use_bn else None, db, coef)
-    dy = torch.empty((m, cin), device="cuda")
-    dz = torch.full((m, c), 7.0, device="cuda")
+    dy = mem.empty((m, cin))
+    dz = mem.full((m, c), 7.0)
     ops.pointwise_bwd_data_bnrelu(dev(da), dev(z), m, cin, cout, dev(pk), ts, th, coef, drop, 55, dy, dz)
     if use_bn:
         rz, rg, rb = K.bn_relu_bwd(da, z, gamma, beta, f32(mean), f32(var), drop=dmult)
@@ -379,7 +415,10 @@ def test_pointwise_bwd_data_bnrelu(ops, use_bn, drop, m, cin, cout):
 
 
 @pytest.mark.parametrize("mode,drop", [(1, 0.0), (1, 0.2), (0, 0.0)])
-@pytest.mark.parametrize("n,h,w,cin,cout", [(2, 4, 4, 64, 32), (2, 3, 5, 32, 16), (1, 8, 8, 128, 64)])
+@pytest.mark.parametrize("n,h,w,cin,cout", [(2, 4, 4, 64, 32), (2, 3, 5, 32, 16), (1, 8, 8, 128, 64),
+                                            # 1, 127 and 129 pixels; 4 * cout = 68 columns, cin 6: scalar kernels
+                                            (1, 1, 1, 64, 32), (1, 1, 127, 64, 17), (1, 3, 43, 64, 32),
+                                            (1, 3, 43, 6, 12)])
 def test_conv_transpose(ops, mode, drop, n, h, w, cin, cout):
     rng = np.random.default_rng(n * h * w + cin)
     a, t = _view_inputs(rng, mode, n, h, w, cin)
@@ -387,13 +426,13 @@ def test_conv_transpose(ops, mode, drop, n, h, w, cin, cout):
     xv = view_value(mode, a["src0"], a.get("sc0"), a.get("sh0"), drop_rate=drop, drop_seed=4242)
     k = f32(rng.standard_normal((2, 2, cout, cin)) / np.sqrt(cin))
     b = f32(rng.standard_normal(cout))
-    out = torch.empty((n, 2 * h, 2 * w, cout), device="cuda")
+    out = mem.empty((n, 2 * h, 2 * w, cout))
     ops.conv_transpose2x2_fwd(v, n, h, w, cout, dev(k), dev(b), out)
     assert rel_err(host(out), K.conv_transpose2x2(xv, k, b)) < 5e-6
     dout = f32(rng.standard_normal((n, 2 * h, 2 * w, cout)))
-    dx = torch.empty((n, h, w, cin), device="cuda")
-    dk = torch.empty((2, 2, cout, cin), device="cuda")
-    db = torch.empty(cout, device="cuda")
+    dx = mem.empty((n, h, w, cin))
+    dk = mem.empty((2, 2, cout, cin))
+    db = mem.empty(cout)
     ops.conv_transpose2x2_bwd(v, n, h, w, cout, dev(k), dev(dout), dx, dk, db)
     rdx, rdk, rdb = K.conv_transpose2x2_bwd(xv, k, dout)
     assert rel_err(host(dx), rdx) < 5e-6
@@ -403,7 +442,8 @@ def test_conv_transpose(ops, mode, drop, n, h, w, cin, cout):
 
 @pytest.mark.parametrize("mode", [0, 1])
 @pytest.mark.parametrize("cin", [32, 64, 128, 256, 48])  # 48: the LDS-tile kernel
-@pytest.mark.parametrize("n,h,w", [(2, 12, 10), (1, 3, 5), (3, 64, 40)])  # ragged pixel counts; > 1 grid pass
+@pytest.mark.parametrize("n,h,w", [(2, 12, 10), (1, 3, 5), (3, 64, 40),  # ragged pixel counts; > 1 grid pass
+                                   (1, 1, 1), (1, 1, 127), (1, 3, 43)])  # 1, 127, 129 pixels
 def test_head_fwd_binary(ops, mode, cin, n, h, w):
     """Binary sigmoid head (u_net.py:105-112) against the float64 oracle."""
     rng = np.random.default_rng(cin + 3 * mode + n * h * w)
@@ -412,7 +452,7 @@ def test_head_fwd_binary(ops, mode, cin, n, h, w):
     xv = view_value(mode, a["src0"], a.get("sc0"), a.get("sh0"))
     k = f32(rng.standard_normal((1, 1, cin, 1)) * 0.2)
     b = f32(rng.standard_normal(1) * 0.1)
-    prob = torch.full((n, h, w, 1), -1.0, device="cuda")
+    prob = mem.full((n, h, w, 1), -1.0)
     ops.head_fwd(v, n, h, w, 1, dev(k), dev(b), prob)
     assert rel_err(host(prob), K.head(xv, k, b, 1)) < 2e-6
 
@@ -427,7 +467,7 @@ def test_head_dice(ops, ncls, loss_kind):
     xv = view_value(1, a["src0"], a["sc0"], a["sh0"])
     k = f32(rng.standard_normal((1, 1, cin, ncls)) * 0.2)
     b = f32(rng.standard_normal(ncls) * 0.1)
-    prob = torch.empty((n, h, w, ncls), device="cuda")
+    prob = mem.empty((n, h, w, ncls))
     ops.head_fwd(v, n, h, w, ncls, dev(k), dev(b), prob)
     rp = K.head(xv, k, b, ncls)
     assert rel_err(host(prob), rp) < 2e-6
@@ -436,17 +476,17 @@ def test_head_dice(ops, ncls, loss_kind):
     else:
         cls = rng.integers(0, ncls, (n, h, w))
         yt = np.eye(ncls)[cls]
-    sums = torch.empty(n * ncls * 3, device="cuda")
-    res = torch.empty(3, device="cuda")
+    sums = mem.empty(n * ncls * 3)
+    res = mem.empty(3)
     ops.dice_fwd(dev(yt), prob, n, h * w, ncls, 1e-7, sums, res)
     pp = host(prob)
     r = host(res)
     assert abs(r[0] - K.dice_loss(yt, pp)) < 1e-6
     assert abs(r[1] - K.dice_coef(yt, pp)) < 1e-6
     assert abs(r[2] - K.iou_coef(yt, pp)) < 1e-6
-    dx = torch.empty((n, h, w, cin), device="cuda")
-    dk = torch.empty((1, 1, cin, ncls), device="cuda")
-    db = torch.empty(ncls, device="cuda")
+    dx = mem.empty((n, h, w, cin))
+    dk = mem.empty((1, 1, cin, ncls))
+    db = mem.empty(ncls)
     ops.head_bwd(v, n, h, w, ncls, dev(k), prob, dev(yt), sums, 1e-7, loss_kind, dx, dk, db)
     dprob = K.dice_loss_grad(yt, pp) if loss_kind == 0 else K.iou_loss_grad(yt, pp)
     rdx, rdk, rdb = K.head_bwd(xv, k, pp, dprob, ncls)
@@ -466,7 +506,10 @@ def test_head_dice(ops, ncls, loss_kind):
 @pytest.mark.parametrize("cin,mode,nhw,unaligned", [(64, 1, (3, 64, 40), False), (16, 0, (2, 13, 11), False),
                                                     (48, 1, (1, 17, 19), False), (128, 1, (1, 9, 7), False),
                                                     (4, 1, (1, 300, 1), False), (64, 1, (2, 17, 19), False),
-                                                    (64, 1, (2, 17, 19), True)])
+                                                    (64, 1, (2, 17, 19), True),
+                                                    # 1, 127 and 129 pixels
+                                                    (64, 1, (1, 1, 1), False), (16, 0, (1, 1, 127), False),
+                                                    (64, 1, (1, 3, 43), False), (48, 1, (1, 3, 43), True)])
 def test_head_multiclass_shapes(ops, ncls, cin, mode, nhw, unaligned):
     """Softmax head forward + dice-loss backward (u_net.py:105-112, losses) over class counts that
     round up to every register width (4..32), ragged and multi-tile pixel counts, tiles that span
@@ -481,26 +524,22 @@ def test_head_multiclass_shapes(ops, ncls, cin, mode, nhw, unaligned):
     k = f32(rng.standard_normal((1, 1, cin, ncls)) * 0.2)
     b = f32(rng.standard_normal(ncls) * 0.1)
 
-    def buf(arr=None):
-        size = n * h * w * ncls
-        base = torch.full((size + 1,), -1.0, device="cuda")
-        out = base[1:] if unaligned else base[:size]
-        if arr is not None:
-            out.copy_(torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32).reshape(-1)))
-        return out.view(n, h, w, ncls)
+    def buf(arr=None):  # unaligned: the arena's skewed tensors, 4 bytes past a 16-byte boundary
+        out = mem.full((n, h, w, ncls), -1.0) if arr is None else dev(arr)
+        return mem.skewed(out) if unaligned else out
     prob = buf()
     ops.head_fwd(v, n, h, w, ncls, dev(k), dev(b), prob)
     pp = host(prob)
     assert rel_err(pp, K.head(xv, k, b, ncls)) < 2e-6
     yt = np.eye(ncls)[rng.integers(0, ncls, (n, h, w))]
     ytd = buf(yt)
-    sums = torch.empty(n * ncls * 3, device="cuda")
-    res = torch.empty(3, device="cuda")
+    sums = mem.empty(n * ncls * 3)
+    res = mem.empty(3)
     ops.dice_fwd(ytd, prob, n, h * w, ncls, 1e-7, sums, res)
     assert abs(host(res)[0] - K.dice_loss(yt, pp)) < 1e-6
-    dx = torch.full((n, h, w, cin), 7.0, device="cuda")
-    dk = torch.empty((1, 1, cin, ncls), device="cuda")
-    db = torch.empty(ncls, device="cuda")
+    dx = mem.full((n, h, w, cin), 7.0)
+    dk = mem.empty((1, 1, cin, ncls))
+    db = mem.empty(ncls)
     ops.head_bwd(v, n, h, w, ncls, dev(k), prob, ytd, sums, 1e-7, 0, dx, dk, db)
     rdx, rdk, rdb = K.head_bwd(xv, k, pp, K.dice_loss_grad(yt, pp), ncls)
     assert rel_err(host(dx), rdx) < 1e-4
@@ -519,14 +558,14 @@ def test_meaniou(ops, ncls, thr):
         yp[::11] = 1.0
     else:
         yp = rng.random(count)
-    conf = torch.zeros(ncls * ncls, dtype=torch.int64, device="cuda")
+    conf = mem.zeros(ncls * ncls, dtype=torch.int64)
     ops.meaniou_update(dev(yt), dev(yp), ncls, thr, conf)
     ops.meaniou_update(dev(yt), dev(yp), ncls, thr, conf)  # accumulates
     ref = 2 * K.meaniou_confusion(f32(yt), f32(yp), ncls, thr)
     assert np.array_equal(conf.cpu().numpy().reshape(ncls, ncls), ref)
     # buffers not 16-byte aligned take the scalar kernel
     conf.zero_()
-    ops.meaniou_update(dev(yt)[1:], dev(yp)[1:], ncls, thr, conf)
+    ops.meaniou_update(mem.skewed(f32(yt)[1:]), mem.skewed(f32(yp)[1:]), ncls, thr, conf)
     ref = K.meaniou_confusion(f32(yt)[1:], f32(yp)[1:], ncls, thr)
     assert np.array_equal(conf.cpu().numpy().reshape(ncls, ncls), ref)
 
@@ -548,11 +587,13 @@ def test_adamw(ops):
 
 def test_errors_are_loud(ops):
     from unet_amd._lib import UnetHipError
-    x = torch.zeros((1, 4, 4, 8), device="cuda")
+    x = mem.zeros((1, 4, 4, 8))
+    out = mem.empty(x.shape, output=False)
     with pytest.raises(UnetHipError):  # workspace / shape validation in the C-ABI
-        ops.dwconv3x3_fwd(ops.View(1, x, 8), 1, 4, 4, torch.zeros(72, device="cuda"), torch.empty_like(x))
+        ops.dwconv3x3_fwd(ops.View(1, x, 8), 1, 4, 4, mem.zeros(72), out)
     with pytest.raises(ValueError):
-        ops.dwconv3x3_fwd(ops.View.plain(x.cpu()), 1, 4, 4, torch.zeros(72), torch.empty_like(x))
+        ops.dwconv3x3_fwd(ops.View.plain(x.cpu()), 1, 4, 4, torch.zeros(72), out)
+    assert mem.is_untouched(out)
 
 
 SEP_CASES = [
@@ -573,6 +614,10 @@ SEP_CASES = [
     (2, 2, 8, 16, 64, 0, 128, 0.2),
     (2, 1, 16, 32, 128, 0, 64, 0.0),
     (1, 4, 128, 128, 64, 0, 192, 0.0),
+    # the smallest supported shape (one 8 x 16 tile), and three images: a partial last block
+    (1, 1, 8, 16, 64, 0, 64, 0.0),
+    (1, 3, 8, 16, 64, 0, 64, 0.0),
+    (3, 3, 8, 16, 64, 64, 128, 0.2),
 ]
 
 
@@ -595,9 +640,9 @@ def test_fused_sepconv(ops, sep_schedule, mode, n, h, w, c0, c1, cout, drop, tra
     v = _mk_view(ops, mode, t, drop, 77)
     assert ops.sepconv_supported(v, n, h, w, cout)
     m = n * h * w
-    y = torch.full((n, h, w, C), -7.0, device="cuda")
-    z = torch.empty((n, h, w, cout), device="cuda")
-    part = torch.zeros(ops.bn_partials_numel(m, cout), device="cuda")
+    y = mem.full((n, h, w, C), -7.0)
+    z = mem.empty((n, h, w, cout))
+    part = mem.zeros(ops.bn_partials_numel(m, cout))
     ops.sepconv_fwd(v, n, h, w, dev(dk), cout, dev(pk), y if train else None, z, part if train else None)
     xv = view_value(mode, a["src0"], a.get("sc0"), a.get("sh0"), a.get("src1"), a.get("sc1"), a.get("sh1"), drop, 77)
     yr = K.depthwise3x3(xv, dk)
@@ -605,7 +650,7 @@ def test_fused_sepconv(ops, sep_schedule, mode, n, h, w, c0, c1, cout, drop, tra
     assert rel_err(host(z), zr) < 5e-6
     if train:
         assert rel_err(host(y), yr) < 2e-6
-        outs = [torch.empty(cout, device="cuda") for _ in range(4)]
+        outs = [mem.empty(cout) for _ in range(4)]
         gamma, beta = bn_affine(rng, cout)
         ops.bn_finalize(part, m, cout, dev(gamma), dev(beta), 1e-3, 0.99, None, None, False, *outs)
         _, mean, var = K.bn_train(zr, gamma, beta)
@@ -630,9 +675,9 @@ def test_sepconv_schedules_bitwise_equal(ops, mode, n, h, w, c0, c1, cout, drop)
     for sch in (ops.SEPCONV_RK, ops.SEPCONV_TILE):
         old = ops.sepconv_set_schedule(sch)
         try:
-            y = torch.empty((n, h, w, C), device="cuda")
-            z = torch.empty((n, h, w, cout), device="cuda")
-            part = torch.zeros(ops.bn_partials_numel(m, cout), device="cuda")
+            y = mem.empty((n, h, w, C))
+            z = mem.empty((n, h, w, cout))
+            part = mem.zeros(ops.bn_partials_numel(m, cout))
             ops.sepconv_fwd(v, n, h, w, dk, cout, pk, y, z, part)
             torch.cuda.synchronize()
             outs.append((y.cpu(), z.cpu(), part.cpu()))
@@ -656,6 +701,8 @@ SW_CASES = [
     (1, 3, 64, 96, 64, 0, 64, 0.0),      # several tiles per block, ragged tiles per block
     (1, 2, 16, 32, 128, 0, 128, 0.0),    # 128 outputs (the 128 x 128 level: enc2_block2 / dec2_block2)
     (3, 1, 16, 32, 128, 128, 128, 0.2),  # 128 outputs, concat + dropout (dec2_block1: 256 -> 128)
+    (1, 1, 8, 16, 64, 0, 64, 0.0),       # the smallest supported shape: one 8 x 16 tile
+    (1, 3, 8, 16, 64, 0, 64, 0.0),       # three images: a partial last block
 ]
 
 
@@ -672,8 +719,8 @@ def test_sepconv_bwd_filter(ops, mode, n, h, w, c0, c1, cout, drop):
     dz = f32(rng.standard_normal((n, h, w, cout)))
     v = _mk_view(ops, mode, t, drop, 41)
     assert ops.sepconv_bwd_filter_supported(v, n, h, w, cout)
-    ddk = torch.empty((3, 3, C, 1), device="cuda")
-    dpk = torch.empty((1, 1, C, cout), device="cuda")
+    ddk = mem.empty((3, 3, C, 1))
+    dpk = mem.empty((1, 1, C, cout))
     ops.sepconv_bwd_filter(v, n, h, w, dev(dk), dev(dy), dev(dz), cout, ddk, dpk)
     xv = view_value(mode, a["src0"], a.get("sc0"), a.get("sh0"), a.get("src1"), a.get("sc1"), a.get("sh1"),
                     drop, 41).astype(np.float64)
@@ -682,11 +729,11 @@ def test_sepconv_bwd_filter(ops, mode, n, h, w, c0, c1, cout, drop):
     _, rdk = K.depthwise3x3_bwd(xv, dk.astype(np.float64), dy.astype(np.float64))
     assert rel_err(host(dpk), rpk) < 1e-5
     assert rel_err(host(ddk), rdk) < 1e-5
-    y = torch.empty((n, h, w, C), device="cuda")
+    y = mem.empty((n, h, w, C))
     ops.sepconv_fwd(v, n, h, w, dev(dk), cout, dev(f32(rng.standard_normal((1, 1, C, cout)))), y,
-                    torch.empty((n, h, w, cout), device="cuda"))
-    g_pk = torch.empty((1, 1, C, cout), device="cuda")
-    g_dk = torch.empty((3, 3, C, 1), device="cuda")
+                    mem.empty((n, h, w, cout)))
+    g_pk = mem.empty((1, 1, C, cout))
+    g_dk = mem.empty((3, 3, C, 1))
     ops.pointwise_bwd_filter(y, dev(dz), n * h * w, C, cout, g_pk)
     ops.dwconv3x3_bwd_filter(v, n, h, w, dev(dy), g_dk)
     assert rel_err(host(dpk), host(g_pk)) < 2e-6
@@ -694,42 +741,43 @@ def test_sepconv_bwd_filter(ops, mode, n, h, w, c0, c1, cout, drop):
 
 
 def test_sepconv_bwd_filter_unsupported(ops):
-    sc = torch.ones(64, device="cuda")
-    x64 = torch.zeros((1, 8, 16, 64), device="cuda")
-    assert not ops.sepconv_bwd_filter_supported(ops.View.plain(torch.zeros((1, 8, 16, 96), device="cuda")),
+    sc = mem.full(64, 1.0)
+    x64 = mem.zeros((1, 8, 16, 64))
+    assert not ops.sepconv_bwd_filter_supported(ops.View.plain(mem.zeros((1, 8, 16, 96))),
                                                 1, 8, 16, 64)  # 96 input channels: not a multiple of 64
     assert not ops.sepconv_bwd_filter_supported(ops.View.plain(x64), 1, 8, 16, 256)  # 256 outputs
-    assert not ops.sepconv_bwd_filter_supported(ops.View.pool_bnrelu(torch.zeros((1, 16, 32, 64), device="cuda"),
+    assert not ops.sepconv_bwd_filter_supported(ops.View.pool_bnrelu(mem.zeros((1, 16, 32, 64)),
                                                                      sc, sc), 1, 8, 16, 64)
     with pytest.raises(Exception):
-        ops.sepconv_bwd_filter(ops.View.plain(x64), 1, 8, 16, torch.zeros(9 * 64, device="cuda"),
-                               torch.zeros(8 * 16 * 64, device="cuda"), torch.zeros(8 * 16 * 256, device="cuda"), 256,
-                               torch.empty(9 * 64, device="cuda"), torch.empty(64 * 256, device="cuda"))
+        ops.sepconv_bwd_filter(ops.View.plain(x64), 1, 8, 16, mem.zeros(9 * 64),
+                               mem.zeros(8 * 16 * 64), mem.zeros(8 * 16 * 256), 256,
+                               mem.empty(9 * 64, output=False), mem.empty(64 * 256, output=False))
 
 
 def test_sepconv_schedule_rk_refuses_narrow(ops):
     """The register-A kernel needs >= 64 input and output channels; forcing it elsewhere errors."""
-    x = torch.zeros((1, 8, 16, 4), device="cuda")
+    x = mem.zeros((1, 8, 16, 4))
     old = ops.sepconv_set_schedule(ops.SEPCONV_RK)
     try:
         with pytest.raises(Exception):
-            ops.sepconv_fwd(ops.View.plain(x), 1, 8, 16, torch.zeros(9 * 4, device="cuda"), 64,
-                            torch.zeros(4 * 64, device="cuda"), None, torch.empty((1, 8, 16, 64), device="cuda"))
+            ops.sepconv_fwd(ops.View.plain(x), 1, 8, 16, mem.zeros(9 * 4), 64,
+                            mem.zeros(4 * 64), None, mem.empty((1, 8, 16, 64), output=False))
     finally:
         ops.sepconv_set_schedule(old)
 
 
 def test_fused_sepconv_unsupported_shapes(ops):
-    x = torch.zeros((1, 8, 8, 16), device="cuda")
+    x = mem.zeros((1, 8, 8, 16))
     assert not ops.sepconv_supported(ops.View.plain(x), 1, 8, 8, 64)     # w % 16 != 0
-    x3 = torch.zeros((1, 16, 16, 3), device="cuda")
+    x3 = mem.zeros((1, 16, 16, 3))
     assert not ops.sepconv_supported(ops.View.plain(x3), 1, 16, 16, 64)  # 3 channels
 
 
 @pytest.mark.parametrize("use_bn", [True, False])
 @pytest.mark.parametrize("drop", [0.0, 0.2])
 @pytest.mark.parametrize("n,h,w,cin,cout", [(2, 8, 8, 128, 64), (1, 5, 7, 64, 32), (3, 4, 6, 256, 128),
-                                            (2, 16, 16, 128, 128), (4, 64, 144, 128, 64)])  # > 256 slabs
+                                            (2, 16, 16, 128, 128), (4, 64, 144, 128, 64),  # > 256 slabs
+                                            (1, 1, 1, 64, 32), (1, 1, 127, 64, 20), (1, 3, 43, 68, 32)])  # 1, 127, 129 px
 def test_convt_bwd_data_bnstats(ops, use_bn, drop, n, h, w, cin, cout):
     """Conv2DTranspose data gradient that also emits the BN-backward partials of the block below
     (u_net.py:88 upsample fed by a BN+ReLU output; with drop > 0 through the bottleneck's Dropout,
@@ -750,16 +798,16 @@ def test_convt_bwd_data_bnstats(ops, use_bn, drop, n, h, w, cin, cout):
     assert S == (m + bm - 1) // bm
     mean = dev(f32(rng.standard_normal(cin) * 0.1))
     rstd = dev(f32(1.0 + rng.random(cin)))
-    part = torch.zeros(ops.bn_stats_partials_numel(S, cin), device="cuda")  # counters zero
-    dx_f, dx_p = torch.empty((n, h, w, cin), device="cuda"), torch.empty((n, h, w, cin), device="cuda")
+    part = mem.zeros(ops.bn_stats_partials_numel(S, cin))  # counters zero
+    dx_f, dx_p = mem.empty((n, h, w, cin)), mem.empty((n, h, w, cin))
     ops.conv_transpose2x2_bwd_data_bnstats(v, n, h, w, cout, k, dout, dx_f, mean if use_bn else None,
                                            rstd if use_bn else None, part)
     ops.conv_transpose2x2_bwd(v, n, h, w, cout, k, dout, dx_p, None, None)
     assert torch.equal(dx_f, dx_p)
     outs = []
     for fused in (True, False):
-        dg, db, coef = (torch.zeros(cin, device="cuda"), torch.zeros(cin, device="cuda"),
-                        torch.empty(3 * cin, device="cuda"))
+        dg, db, coef = (mem.zeros(cin), mem.zeros(cin),
+                        mem.empty(3 * cin))
         if fused:
             ops.bn_relu_bwd_stats_finish(part, S, m, cin, mean, rstd, use_bn, dg if use_bn else None, db, coef)
             assert not torch.any(part[-((cin + 63) // 64):].view(torch.int32))
@@ -783,7 +831,8 @@ def test_convt_bwd_data_bnstats(ops, use_bn, drop, n, h, w, cin, cout):
 @pytest.mark.parametrize("mode", [2, 1])
 @pytest.mark.parametrize("use_bn", [True, False])
 @pytest.mark.parametrize("n,h,w,c", [(2, 8, 16, 64), (2, 5, 7, 16), (1, 4, 4, 128), (3, 8, 8, 8),
-                                     (4, 64, 144, 64)])  # > 256 slabs: two-pass finish
+                                     (4, 64, 144, 64),  # > 256 slabs: two-pass finish
+                                     (1, 1, 1, 8), (1, 1, 127, 16), (1, 3, 43, 32)])  # 1, 127, 129 pixels
 def test_dwconv_bwd_data_bnstats(ops, mode, use_bn, n, h, w, c):
     """Pool / BN+ReLU-view data gradient that also emits the view block's BN-backward partials:
     dx0 bitwise equal to the plain launch, statistics equal to unet_bn_relu_bwd_stats's."""
@@ -798,8 +847,8 @@ def test_dwconv_bwd_data_bnstats(ops, mode, use_bn, n, h, w, c):
     assert S > 0
     mean = dev(f32(rng.standard_normal(c) * 0.1))
     rstd = dev(f32(1.0 + rng.random(c)))
-    part = torch.zeros(ops.bn_stats_partials_numel(S, c), device="cuda")  # counters zero
-    dx_f, dx_p = dev(init), dev(init)
+    part = mem.zeros(ops.bn_stats_partials_numel(S, c))  # counters zero
+    dx_f, dx_p = mem.inp(init, fence=mem.out_fence), mem.inp(init, fence=mem.out_fence)
     ops.dwconv3x3_bwd_data_bnstats(v, n, h, w, dk, dy, dx_f, mean if use_bn else None, rstd if use_bn else None,
                                    part)
     ops.dwconv3x3_bwd_data(v, n, h, w, dk, dy, dx_p)
@@ -807,11 +856,11 @@ def test_dwconv_bwd_data_bnstats(ops, mode, use_bn, n, h, w, c):
     m = n * f * f * h * w
     outs = []
     for fused in (True, False):
-        dg, db, coef = (torch.zeros(c, device="cuda"), torch.zeros(c, device="cuda"),
-                        torch.empty(3 * c, device="cuda"))
+        dg, db, coef = (mem.zeros(c), mem.zeros(c),
+                        mem.empty(3 * c))
         if fused:  # twice: the arrival counters are left zero, the result is deterministic
             ops.bn_relu_bwd_stats_finish(part, S, m, c, mean, rstd, use_bn, dg if use_bn else None, db, coef)
-            first = coef.clone()
+            first = mem.inp(coef)
             ops.bn_relu_bwd_stats_finish(part, S, m, c, mean, rstd, use_bn, dg if use_bn else None, db, coef)
             assert torch.equal(first, coef)
             assert not torch.any(part[-((c + 63) // 64):].view(torch.int32))
@@ -851,18 +900,18 @@ def test_head_bwd_bnstats(ops, use_bn, loss_kind, ncls, nhw):
         lg = rng.standard_normal((n, h, w, ncls))
         prob = dev(f32(np.exp(lg) / np.exp(lg).sum(-1, keepdims=True)))
         yt = dev(f32(np.eye(ncls)[rng.integers(0, ncls, (n, h, w))]))
-    sums = torch.empty(n * ncls * 3, device="cuda")
-    res = torch.empty(3, device="cuda")
+    sums = mem.empty(n * ncls * 3)
+    res = mem.empty(3)
     ops.dice_fwd(yt, prob, n, h * w, ncls, 1e-7, sums, res)
     S = ops.head_bwd_bnstats_slabs(v, n, h, w, ncls)
     assert S > 0
     mean = dev(f32(rng.standard_normal(c) * 0.1))
     rstd = dev(f32(1.0 + rng.random(c)))
-    part = torch.zeros(ops.bn_stats_partials_numel(S, c), device="cuda")  # counters zero
+    part = mem.zeros(ops.bn_stats_partials_numel(S, c))  # counters zero
     outs = []
     for fused in (True, False):
-        dx, dk, db = (torch.empty((n, h, w, c), device="cuda"), torch.empty(c * ncls, device="cuda"),
-                      torch.empty(ncls, device="cuda"))
+        dx, dk, db = (mem.empty((n, h, w, c)), mem.empty(c * ncls),
+                      mem.empty(ncls))
         if fused:
             ops.head_bwd_bnstats(v, n, h, w, ncls, k, prob, yt, sums, 1e-7, loss_kind, dx, dk, db,
                                  mean if use_bn else None, rstd if use_bn else None, part)
@@ -874,8 +923,8 @@ def test_head_bwd_bnstats(ops, use_bn, loss_kind, ncls, nhw):
     if ncls == 1:
         # rank-one form (ABI 10): only dL/dlogit per pixel goes out; dx == dlogit (x) kernel bitwise,
         # the same weight / bias gradients and BN-backward partials
-        dl, dk1, db1 = torch.empty(n * h * w, device="cuda"), torch.empty(c, device="cuda"), torch.empty(1, device="cuda")
-        part1 = torch.zeros_like(part)
+        dl, dk1, db1 = mem.empty(n * h * w), mem.empty(c), mem.empty(1)
+        part1 = mem.zeros(part.shape)
         ops.head_bwd_bnstats(v, n, h, w, 1, k, prob, yt, sums, 1e-7, loss_kind, None, dk1, db1,
                              mean if use_bn else None, rstd if use_bn else None, part1, dlogit=dl)
         assert torch.equal(dl[:, None] * k.reshape(1, c), outs[0][0].reshape(-1, c))
@@ -886,7 +935,7 @@ def test_head_bwd_bnstats(ops, use_bn, loss_kind, ncls, nhw):
     m = n * h * w
     st = []
     for fused in (True, False):
-        dg, dbb, coef = torch.zeros(c, device="cuda"), torch.zeros(c, device="cuda"), torch.empty(3 * c, device="cuda")
+        dg, dbb, coef = mem.zeros(c), mem.zeros(c), mem.empty(3 * c)
         if fused:
             ops.bn_relu_bwd_stats_finish(part, S, m, c, mean, rstd, use_bn, dg if use_bn else None, dbb, coef)
         else:
@@ -899,15 +948,15 @@ def test_head_bwd_bnstats(ops, use_bn, loss_kind, ncls, nhw):
 
 def test_copy_strided(ops):
     """Channel padding (3 -> 4, pad channel untouched) and slicing back, bit-exact."""
-    x = torch.randn(2, 8, 16, 3, device="cuda")
-    xp = torch.full((2, 8, 16, 4), 7.0, device="cuda")
+    x = dev(np.random.default_rng(1).standard_normal((2, 8, 16, 3)))
+    xp = mem.full((2, 8, 16, 4), 7.0)
     ops.copy_strided(x, 2 * 8 * 16, 3, 3, xp, 4)
     assert torch.equal(xp[..., :3], x) and bool((xp[..., 3] == 7.0).all())
-    back = torch.empty(2, 8, 16, 3, device="cuda")
+    back = mem.empty((2, 8, 16, 3))
     ops.copy_strided(xp, 2 * 8 * 16, 3, 4, back, 3)
     assert torch.equal(back, x)
-    pk = torch.randn(1, 1, 3, 64, device="cuda")
-    pp = torch.zeros(1, 1, 4, 64, device="cuda")
+    pk = dev(np.random.default_rng(2).standard_normal((1, 1, 3, 64)))
+    pp = mem.zeros((1, 1, 4, 64))
     ops.copy_strided(pk, 1, 3 * 64, 3 * 64, pp, 4 * 64)
     assert torch.equal(pp[:, :, :3], pk) and not pp[:, :, 3].any()
     with pytest.raises(ValueError):
@@ -930,7 +979,7 @@ def test_pool_select(ops, n, h, w, c):
     gamma[:2] = [0.0, -0.0]
     rstd = f32(0.5 + rng.random(c))
     scale, shift = f32(gamma * rstd), f32(rng.standard_normal(c) * 0.3)
-    out = torch.empty((n, h // 2, w // 2, c), device="cuda")
+    out = mem.empty((n, h // 2, w // 2, c))
     for g, sc in ((gamma, scale), (None, np.ones(c, np.float32))):
         ops.pool_select(dev(z), n, h, w, c, None if g is None else dev(g), out)
         tz, tsc, tsh = dev(z), dev(sc), dev(shift)
@@ -951,10 +1000,10 @@ def test_sepconv_pool_selection_epilogue(ops, sep_schedule, mode, n, h, w, c0, c
     pk = dev(f32(rng.standard_normal((1, 1, c0, cout)) / np.sqrt(c0)))
     v = _mk_view(ops, mode, t)
     gamma = dev(f32(rng.standard_normal(cout)))
-    z = torch.empty((n, h, w, cout), device="cuda")
-    zsel = torch.full((n, h // 2, w // 2, cout), 7.0, device="cuda")
+    z = mem.empty((n, h, w, cout))
+    zsel = mem.full((n, h // 2, w // 2, cout), 7.0)
     ops.sepconv_fwd(v, n, h, w, dk, cout, pk, None, z, None, zsel, gamma)
-    ref = torch.empty_like(zsel)
+    ref = mem.empty(zsel.shape)
     ops.pool_select(z, n, h, w, cout, gamma, ref)
     assert torch.equal(zsel, ref)
 
@@ -968,15 +1017,15 @@ def test_sepconv_pool_selection_epilogue_split_precision(ops, n, h, w, c0, cout)
     a, t = _view_inputs(rng, 1, n, h, w, c0, 0)
     dk = dev(f32(rng.standard_normal((3, 3, c0, 1))))
     pk = dev(f32(rng.standard_normal((1, 1, c0, cout)) / np.sqrt(c0)))
-    pkx = torch.empty(3 * c0 * cout, dtype=torch.int16, device="cuda")
+    pkx = mem.empty(3 * c0 * cout, dtype=torch.int16)
     ops.split_x3(pk, [(0, c0, cout, 0)], pkx)
     v = _mk_view(ops, 1, t)
     gamma = dev(f32(rng.standard_normal(cout)))
-    z = torch.empty((n, h, w, cout), device="cuda")
-    zsel = torch.full((n, h // 2, w // 2, cout), 7.0, device="cuda")
-    part = torch.zeros(ops.bn_partials_numel(n * h * w, cout), device="cuda")
+    z = mem.empty((n, h, w, cout))
+    zsel = mem.full((n, h // 2, w // 2, cout), 7.0)
+    part = mem.zeros(ops.bn_partials_numel(n * h * w, cout))
     ops.sepconv_fwd(v, n, h, w, dk, cout, pk, None, z, part, zsel, gamma, pkx=pkx)
-    ref = torch.empty_like(zsel)
+    ref = mem.empty(zsel.shape)
     ops.pool_select(z, n, h, w, cout, gamma, ref)
     assert torch.equal(zsel, ref)
     zr = K.pointwise(K.depthwise3x3(view_value(1, a["src0"], a["sc0"], a["sh0"], None, None, None, 0.0, 0), host(dk)),
@@ -999,7 +1048,7 @@ def test_fused_sepconv_split_precision(ops, mode, n, h, w, c0, c1, cout, drop):
     dk = dev(f32(rng.standard_normal((3, 3, C, 1))))
     pk32 = f32(rng.standard_normal((1, 1, C, cout)) / np.sqrt(C))
     pk = dev(pk32)
-    pkx = torch.empty(3 * C * cout, dtype=torch.int16, device="cuda")
+    pkx = mem.empty(3 * C * cout, dtype=torch.int16)
     ops.split_x3(pk, [(0, C, cout, 0)], pkx)
     # the planes hold the exact three-way split, transposed
     hm = pkx.view(3, cout, C).cpu().numpy().astype(np.uint16).astype(np.uint32) << 16
@@ -1009,9 +1058,9 @@ def test_fused_sepconv_split_precision(ops, mode, n, h, w, c0, c1, cout, drop):
     m = n * h * w
     outs = {}
     for tag, px in (("f32", None), ("x6", pkx)):
-        y = torch.full((n, h, w, C), -7.0, device="cuda")
-        z = torch.empty((n, h, w, cout), device="cuda")
-        part = torch.zeros(ops.bn_partials_numel(m, cout), device="cuda")
+        y = mem.full((n, h, w, C), -7.0)
+        z = mem.empty((n, h, w, cout))
+        part = mem.zeros(ops.bn_partials_numel(m, cout))
         ops.sepconv_fwd(v, n, h, w, dk, cout, pk, y, z, part, pkx=px)
         outs[tag] = (y, z, part)
     xv = view_value(mode, a["src0"], a.get("sc0"), a.get("sh0"), a.get("src1"), a.get("sc1"), a.get("sh1"), drop, 77)
@@ -1033,6 +1082,8 @@ PX_CASES = [
     (1, 4, 128, 128, 128, 0, 128, 0.0, True, True),   # enc2_block2's shape at batch 4
     (3, 2, 256, 256, 64, 64, 64, 0.0, True, False),   # dec1_block1's shape at batch 2
     (1, 2, 256, 256, 64, 0, 64, 0.0, True, True),     # enc1_block2's shape (64 -> 64)
+    (1, 1, 8, 16, 64, 0, 64, 0.0, True, True),        # the smallest supported shape: one tile, one block
+    (3, 3, 8, 16, 64, 64, 128, 0.2, True, False),     # three tiles
 ]
 
 
@@ -1049,7 +1100,7 @@ def test_sepconv_persistent_matches_one_tile(ops, mode, n, h, w, c0, c1, cout, d
     dk = dev(f32(rng.standard_normal((3, 3, C, 1))))
     pk32 = f32(rng.standard_normal((1, 1, C, cout)) / np.sqrt(C))
     pk = dev(pk32)
-    pkx = torch.empty(3 * C * cout, dtype=torch.int16, device="cuda")
+    pkx = mem.empty(3 * C * cout, dtype=torch.int16)
     ops.split_x3(pk, [(0, C, cout, 0)], pkx)
     gamma = dev(f32(rng.standard_normal(cout))) if zsel else None
     v = _mk_view(ops, mode, t, drop, 31)
@@ -1058,10 +1109,10 @@ def test_sepconv_persistent_matches_one_tile(ops, mode, n, h, w, c0, c1, cout, d
     for sch in (ops.SEPCONV_RK1, ops.SEPCONV_RK):
         old = ops.sepconv_set_schedule(sch)
         try:
-            y = torch.full((n, h, w, C), -7.0, device="cuda") if train else None
-            z = torch.full((n, h, w, cout), float("nan"), device="cuda")
-            part = torch.zeros(ops.bn_partials_numel(m, cout), device="cuda") if train else None
-            zs = torch.full((n, h // 2, w // 2, cout), float("nan"), device="cuda") if zsel else None
+            y = mem.full((n, h, w, C), -7.0) if train else None
+            z = mem.full((n, h, w, cout), float("nan"))
+            part = mem.zeros(ops.bn_partials_numel(m, cout)) if train else None
+            zs = mem.full((n, h // 2, w // 2, cout), float("nan")) if zsel else None
             ops.sepconv_fwd(v, n, h, w, dk, cout, pk, y, z, part, zs, gamma, pkx=pkx)
             torch.cuda.synchronize()
             outs.append([None if q is None else q.cpu() for q in (y, z, part, zs)])
@@ -1084,7 +1135,8 @@ def test_sepconv_persistent_matches_one_tile(ops, mode, n, h, w, c0, c1, cout, d
 
 
 @pytest.mark.parametrize("mode,n,h,w,c0,c1", [(1, 2, 8, 16, 64, 0), (1, 1, 16, 32, 64, 0), (3, 1, 8, 32, 64, 64),
-                                              (0, 2, 16, 16, 128, 0)])
+                                              (0, 2, 16, 16, 128, 0),
+                                              (1, 1, 8, 16, 64, 0), (1, 3, 8, 16, 64, 0)])  # one tile; three images
 @pytest.mark.parametrize("use_bn", [True, False])
 def test_sepconv_bwd_fused(ops, mode, n, h, w, c0, c1, use_bn):
     """The fused 64-output block backward (unet_sepconv_bwd_fused) against the route it replaces:
@@ -1107,17 +1159,17 @@ def test_sepconv_bwd_fused(ops, mode, n, h, w, c0, c1, use_bn):
         mean = var = rstd = np.zeros(cout)
         scale, shift = np.ones(cout, np.float32), f32(beta)
     ts, th, tz, tda = dev(scale), dev(shift), dev(z), dev(da)
-    coef = torch.empty(3 * cout, device="cuda")
-    dg, db = torch.zeros(cout, device="cuda"), torch.zeros(cout, device="cuda")
+    coef = mem.empty(3 * cout)
+    dg, db = mem.zeros(cout), mem.zeros(cout)
     ops.bn_relu_bwd_stats(tda, tz, m, cout, dev(f32(mean)), dev(f32(rstd)), ts, th, use_bn, 0.0, 0,
                           dg if use_bn else None, db, coef)
     v = _mk_view(ops, mode, t)
-    dy_f = torch.full((n, h, w, C), 7.0, device="cuda")
-    ddk_f, dpk_f = torch.empty((3, 3, C, 1), device="cuda"), torch.empty((1, 1, C, cout), device="cuda")
+    dy_f = mem.full((n, h, w, C), 7.0)
+    ddk_f, dpk_f = mem.empty((3, 3, C, 1)), mem.empty((1, 1, C, cout))
     ops.sepconv_bwd_fused(v, n, h, w, dk, pk, tda, tz, ts, th, coef, cout, dy_f, ddk_f, dpk_f)
-    dy_r, dz_r = torch.empty((m, C), device="cuda"), torch.empty((m, cout), device="cuda")
+    dy_r, dz_r = mem.empty((m, C)), mem.empty((m, cout))
     ops.pointwise_bwd_data_bnrelu(tda, tz, m, C, cout, pk, ts, th, coef, 0.0, 0, dy_r, dz_r)
-    ddk_r, dpk_r = torch.empty((3, 3, C, 1), device="cuda"), torch.empty((1, 1, C, cout), device="cuda")
+    ddk_r, dpk_r = mem.empty((3, 3, C, 1)), mem.empty((1, 1, C, cout))
     ops.sepconv_bwd_filter(v, n, h, w, dk, dy_r, dz_r, cout, ddk_r, dpk_r)
     assert rel_err(host(dy_f).reshape(m, C), host(dy_r)) < 2e-6
     assert rel_err(host(dpk_f), host(dpk_r)) < 2e-6
@@ -1128,8 +1180,8 @@ def test_sepconv_bwd_fused(ops, mode, n, h, w, c0, c1, use_bn):
     da1 = dlg[:, None] * hk[None, :]
     outs1 = []
     for r1 in (False, True):
-        dy1 = torch.full((n, h, w, C), 7.0, device="cuda")
-        ddk1, dpk1 = torch.empty((3, 3, C, 1), device="cuda"), torch.empty((1, 1, C, cout), device="cuda")
+        dy1 = mem.full((n, h, w, C), 7.0)
+        ddk1, dpk1 = mem.empty((3, 3, C, 1)), mem.empty((1, 1, C, cout))
         if r1:
             ops.sepconv_bwd_fused(v, n, h, w, dk, pk, None, tz, ts, th, coef, cout, dy1, ddk1, dpk1, da_rank1=(dlg, hk))
         else:

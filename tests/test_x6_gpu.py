@@ -11,7 +11,8 @@ u_net.py:88-94 (Conv2DTranspose); the six-product split is common.h split4 / mfm
 import numpy as np
 import pytest
 
-from helpers import bn_affine, dev, f32, host, rel_err
+import fenced
+from helpers import bn_affine, f32, host, rel_err
 from oracle import keras_ops as K
 
 pytestmark = pytest.mark.gpu
@@ -30,9 +31,29 @@ def ops():
     return O
 
 
+mem = None  # the running test's fenced.Arena, set by _fenced
+
+
+@pytest.fixture(autouse=True)
+def _fenced(ops):
+    """Every allocation of a test goes through `mem`; workspaces have exactly the queried size.
+    After the body: no fence byte changed and every `mem.empty` output was written in full."""
+    global mem
+    mem = fenced.Arena("cuda")
+    ws = fenced.FencedWorkspace("cuda")
+    with ws.installed(ops):
+        yield mem
+        mem.check(extra=[ws])
+    mem = None
+
+
+def dev(a):
+    return mem.inp(a)
+
+
 def _planes(ops, w2d: np.ndarray, keep: bool):
     rows, cols = w2d.shape
-    t = torch.empty(3 * rows * cols, dtype=torch.int16, device="cuda")
+    t = mem.empty(3 * rows * cols, dtype=torch.int16)
     ops.split_x3(dev(f32(w2d)), [(0, rows, cols, 0)], t, keep=keep)
     return t
 
@@ -81,12 +102,12 @@ def test_pointwise_bwd_data_bnrelu_x3(ops, drop, m, cin, cout):
     pk = f32(rng.standard_normal((cin, cout)) / np.sqrt(cout))
     pkd = _planes(ops, pk, keep=True)
     ts, th = dev(scale), dev(shift)
-    dg, db, coef = torch.zeros(cout, device="cuda"), torch.zeros(cout, device="cuda"), torch.empty(3 * cout, device="cuda")
+    dg, db, coef = mem.zeros(cout), mem.zeros(cout), mem.empty(3 * cout)
     ops.bn_relu_bwd_stats(dev(da), dev(z), m, cout, dev(mean), dev(rstd), ts, th, True, drop, 55, dg, db, coef)
     out = {}
     for key in ("f32", "x6"):
-        dy = torch.full((m, cin), 7.0, device="cuda")
-        dz = torch.full((m, cout), 7.0, device="cuda")
+        dy = mem.full((m, cin), 7.0)
+        dz = mem.full((m, cout), 7.0)
         ops.pointwise_bwd_data_bnrelu(dev(da), dev(z), m, cin, cout, dev(pk), ts, th, coef, drop, 55, dy, dz,
                                       pkd=pkd if key == "x6" else None)
         out[key] = (host(dy), host(dz))
@@ -116,8 +137,8 @@ def test_pointwise_fwd_x3(ops, stats, m, cin, cout):
     pkx = _planes(ops, pk, keep=False)
     res = {}
     for key in ("f32", "x6"):
-        z = torch.full((m, cout), 7.0, device="cuda")
-        part = torch.zeros(ops.bn_partials_numel(m, cout), device="cuda") if stats else None
+        z = mem.full((m, cout), 7.0)
+        part = mem.zeros(ops.bn_partials_numel(m, cout)) if stats else None
         ops.pointwise_fwd(dev(y), m, cin, cout, dev(pk), z, part, pkx=pkx if key == "x6" else None)
         res[key] = (host(z), host(part) if stats else None)
     ref = y.astype(np.float64) @ pk.astype(np.float64)
@@ -148,7 +169,7 @@ def test_conv_transpose_fwd_x3(ops, drop, n, h, w, cin, cout):
     kx = _planes(ops, k.reshape(4 * cout, cin), keep=True)
     out = {}
     for key in ("f32", "x6"):
-        o = torch.full((n, 2 * h, 2 * w, cout), 7.0, device="cuda")
+        o = mem.full((n, 2 * h, 2 * w, cout), 7.0)
         ops.conv_transpose2x2_fwd(v, n, h, w, cout, dev(k), dev(b), o, kx=kx if key == "x6" else None)
         out[key] = host(o)
     ref = K.conv_transpose2x2(x.astype(np.float64), k, b)
@@ -179,12 +200,11 @@ def test_convt_bwd_data_bnstats_x3(ops, drop, n, h, w, cin, cout):
     m = n * h * w
     res = {}
     for key in ("f32", "x6"):
-        part = torch.zeros(ops.bn_stats_partials_numel(S, cin), device="cuda")
-        dx = torch.full((n, h, w, cin), 7.0, device="cuda")
+        part = mem.zeros(ops.bn_stats_partials_numel(S, cin))
+        dx = mem.full((n, h, w, cin), 7.0)
         ops.conv_transpose2x2_bwd_data_bnstats(v, n, h, w, cout, dev(k), dev(dout), dx, mean, rstd, part,
                                                kxt=kxt if key == "x6" else None)
-        dg, db, coef = torch.zeros(cin, device="cuda"), torch.zeros(cin, device="cuda"), torch.empty(3 * cin,
-                                                                                                     device="cuda")
+        dg, db, coef = mem.zeros(cin), mem.zeros(cin), mem.empty(3 * cin)
         ops.bn_relu_bwd_stats_finish(part, S, m, cin, mean, rstd, True, dg, db, coef)
         res[key] = (host(dx), host(dg), host(db))
     ref = np.einsum("niajbd,abdc->nijc", dout.astype(np.float64).reshape(n, h, 2, w, 2, cout), k.astype(np.float64))
@@ -203,7 +223,7 @@ def test_pointwise_bwd_filter_fp32_route(ops, m, cin, cout):
     rng = np.random.default_rng(m + cin + cout)
     y = f32(rng.standard_normal((m, cin)))
     dz = f32(rng.standard_normal((m, cout)))
-    dpk = torch.full((cin, cout), 7.0, device="cuda")
+    dpk = mem.full((cin, cout), 7.0)
     ops.pointwise_bwd_filter(dev(y), dev(dz), m, cin, cout, dpk)
     ref = y.astype(np.float64).T @ dz.astype(np.float64)
     assert rel_err(host(dpk), ref) < TOL
@@ -225,8 +245,8 @@ def test_conv_transpose_bwd_filter_fp32_route(ops, drop, n, h, w, cin, cout):
         x = x * K.dropout_mult(4242, x.shape, drop)
     k = f32(rng.standard_normal((2, 2, cout, cin)) * 0.1)
     dout = f32(rng.standard_normal((n, 2 * h, 2 * w, cout)))
-    dk = torch.full((2, 2, cout, cin), 7.0, device="cuda")
-    db = torch.full((cout,), 7.0, device="cuda")
+    dk = mem.full((2, 2, cout, cin), 7.0)
+    db = mem.full((cout,), 7.0)
     ops.conv_transpose2x2_bwd(v, n, h, w, cout, dev(k), dev(dout), None, dk, db)
     d6 = dout.astype(np.float64).reshape(n, h, 2, w, 2, cout)
     rdk = np.einsum("niajbd,nijc->abdc", d6, x)
@@ -240,9 +260,9 @@ def test_split_x3_mixed(ops):
     rng = np.random.default_rng(77)
     src = dev(f32(rng.standard_normal(5000)))
     segs = [(0, 40, 30, 0, 1), (1200, 16, 48, 3600, 0), (2000, 33, 17, 6000, 1)]
-    mixed = torch.zeros(8000, dtype=torch.int16, device="cuda")
+    mixed = mem.zeros(8000, dtype=torch.int16)
     ops.split_x3(src, segs, mixed)
-    ref = torch.zeros(8000, dtype=torch.int16, device="cuda")
+    ref = mem.zeros(8000, dtype=torch.int16)
     for so, r, c, do, k in segs:
         ops.split_x3(src, [(so, r, c, do)], ref, keep=bool(k))
     assert torch.equal(mixed, ref)

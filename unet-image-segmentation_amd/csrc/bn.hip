@@ -232,9 +232,11 @@ struct RedPlan {
     int ctiles, CT;
     int64_t chunks, rpc;
 };
-RedPlan red_plan(int64_t rows, int cols) {
+// vec = false: one column per lane although cols % 4 == 0 (a source that is not 16-B aligned); it
+// never asks for more chunks than the vec plan, so the workspace queries (vec plan) cover it
+RedPlan red_plan(int64_t rows, int cols, bool vec = true) {
     RedPlan p;
-    const int CQ = cols % 4 == 0 ? cols / 4 : cols;
+    const int CQ = vec && cols % 4 == 0 ? cols / 4 : cols;
     p.CT = CQ < 64 ? CQ : 64;
     p.ctiles = (int)cdiv(CQ, p.CT);
     int64_t want = cdiv(1024, p.ctiles);
@@ -580,12 +582,13 @@ size_t colsum_workspace(int64_t rows, int cols) {
 }
 
 int colsum(const float* x, int64_t rows, int cols, float* out, void* ws, size_t ws_bytes, hipStream_t st) {
-    RedPlan p = red_plan(rows, cols);
+    const bool vec = cols % 4 == 0 && (uintptr_t)x % 16 == 0;  // float4 loads of x
+    RedPlan p = red_plan(rows, cols, vec);
     const size_t need = (size_t)p.chunks * cols * sizeof(float);
     UNET_CHECK_ARG(ws && ws_bytes >= need, "colsum: workspace %zu < %zu", ws_bytes, need);
     float* part = static_cast<float*>(ws);
     dim3 grid(p.ctiles, (unsigned)p.chunks);
-    if (cols % 4 == 0)
+    if (vec)
         colsum_kernel<true><<<grid, 256, 0, st>>>(x, rows, cols, p.CT, p.rpc, part);
     else
         colsum_kernel<false><<<grid, 256, 0, st>>>(x, rows, cols, p.CT, p.rpc, part);

@@ -73,11 +73,21 @@ __global__ __launch_bounds__(256) void head_fwd_bin_kernel(DView v, int64_t M, c
     }
 }
 
+// Channels [c, c + 4) of row m for the two general forward kernels.  al = false: src0 is only 4-byte
+// aligned (the caller's predicate sent it here), so the row is read element by element.
+template <int MODE>
+__device__ __forceinline__ float4 head_row4(const DView& v, int64_t m, int c, bool al) {
+    if (al) return row_load4<MODE, false>(v, m, c);
+    return make_float4(row_load1<MODE, false>(v, m, c), row_load1<MODE, false>(v, m, c + 1),
+                       row_load1<MODE, false>(v, m, c + 2), row_load1<MODE, false>(v, m, c + 3));
+}
+
 // Pixel tile of TP = 8192 / Cin (binary) or 4096 / Cin (multi-class) pixels: the tile's activations are staged through LDS with
 // coalesced float4 loads (one lane per channel quad), then one lane per pixel forms the logits.
 template <int MODE, int NC>
 __global__ __launch_bounds__(256) void head_fwd_kernel(DView v, int64_t M, int ncls, const float* __restrict__ W,
-                                                       const float* __restrict__ bias, float* __restrict__ prob) {
+                                                       const float* __restrict__ bias, float* __restrict__ prob,
+                                                       bool al) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int Cin = v.c0, CQ = Cin / 4, LA = Cin + 1, TP = min(256, (NC == 1 ? 8192 : 4096) / Cin);  // LDS <= 64 KB
     float* Ws = smem;                // [Cin][NC]
@@ -94,7 +104,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(DView v, int64_t M, int n
             const int p = idx / CQ, kq = idx - (idx / CQ) * CQ;
             const int64_t m = m0 + p;
             float4 x = f4(0.f);
-            if (m < M) x = row_load4<MODE, false>(v, m, 4 * kq);
+            if (m < M) x = head_row4<MODE>(v, m, 4 * kq, al);
             float* a = A + p * LA + 4 * kq;
             a[0] = x.x;
             a[1] = x.y;
@@ -511,7 +521,8 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(int64_t M, int64_t hw, in
 // LDS-bound: 153 us per batch-8 forward, profiles/r4j_cfg4_trace.txt.)
 template <int MODE, int NC>
 __global__ __launch_bounds__(256) void head_fwdm_kernel(DView v, int64_t M, int ncls, const float* __restrict__ W,
-                                                        const float* __restrict__ bias, float* __restrict__ prob) {
+                                                        const float* __restrict__ bias, float* __restrict__ prob,
+                                                        bool al) {
     constexpr int CMAX = 64, LA = CMAX + 4;
     __shared__ __attribute__((aligned(16))) float Ws[CMAX * NC];
     __shared__ __attribute__((aligned(16))) float A[256 * LA];
@@ -528,7 +539,7 @@ __global__ __launch_bounds__(256) void head_fwdm_kernel(DView v, int64_t M, int 
         for (int idx = threadIdx.x; idx < 256 * CQ; idx += 256) {
             const int p = idx / CQ, kq = idx - p * CQ;
             const int64_t m = m0 + p;
-            const float4 x = m < M ? row_load4<MODE, false>(v, m, 4 * kq) : f4(0.f);
+            const float4 x = m < M ? head_row4<MODE>(v, m, 4 * kq, al) : f4(0.f);
             *reinterpret_cast<float4*>(&A[p * LA + 4 * kq]) = x;
         }
         __syncthreads();
@@ -1047,6 +1058,7 @@ extern "C" int unet_head_fwd(const unet_view* x, int n, int h, int w, int ncls, 
     const DView v = make_dview(*x);
     const int64_t M = (int64_t)n * h * w;
     hipStream_t st = as_stream(stream);
+    const bool src_al = (uintptr_t)x->src0 % 16 == 0;  // else the general kernels read src0 by elements
     const bool bin_vec = ncls == 1 && (x->c0 == 32 || x->c0 == 64 || x->c0 == 128 || x->c0 == 256) &&
                          ((uintptr_t)x->src0 | (uintptr_t)kernel) % 16 == 0;
     if (bin_vec) {
@@ -1077,7 +1089,7 @@ extern "C" int unet_head_fwd(const unet_view* x, int n, int h, int w, int ncls, 
         const int grid = grid_for(M, 4096);
         with_int<UNET_VIEW_BNRELU, UNET_VIEW_PLAIN>(x->mode, [&](auto MODE) {
             with_bucket<4, 8, 16, 24, 32>(ncls, [&](auto NC) {
-                head_fwdm_kernel<MODE(), NC()><<<grid, 256, 0, st>>>(v, M, ncls, kernel, bias, prob);
+                head_fwdm_kernel<MODE(), NC()><<<grid, 256, 0, st>>>(v, M, ncls, kernel, bias, prob, src_al);
             });
         });
         UNET_CHECK_LAUNCH("unet_head_fwd");
@@ -1091,7 +1103,8 @@ extern "C" int unet_head_fwd(const unet_view* x, int n, int h, int w, int ncls, 
                          (size_t)TP * (x->c0 + 1)) * sizeof(float);
     with_int<UNET_VIEW_BNRELU, UNET_VIEW_PLAIN>(x->mode, [&](auto MODE) {
         with_bool(multi, [&](auto MULTI) {
-            head_fwd_kernel<MODE(), MULTI() ? kMaxCls : 1><<<grid, 256, smem, st>>>(v, M, ncls, kernel, bias, prob);
+            head_fwd_kernel<MODE(), MULTI() ? kMaxCls : 1><<<grid, 256, smem, st>>>(v, M, ncls, kernel, bias, prob,
+                                                                                    src_al);
         });
     });
     UNET_CHECK_LAUNCH("unet_head_fwd");

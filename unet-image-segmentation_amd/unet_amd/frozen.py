@@ -515,8 +515,8 @@ def _split_channels(sources, channels: int):
 def collect_ranges(model_or_frozen, x, batch_size: Optional[int] = None) -> Dict[str, float]:
     """Calibration: max |.| of every calibration_names tensor over the images x (numpy array or
     device tensor (N, H, W, C)).  Runs the fp16 FrozenUNet with keep_activations per batch and
-    keeps running maxima; each `<block>/y` is the fp32 depthwise 3x3 of the kept block input.
-    Needs the GPU; off the hot path."""
+    keeps running maxima; each `<block>/y` is the fp32 depthwise 3x3 of the kept block input.  The
+    result does not depend on batch_size.  Needs the GPU; off the hot path."""
     import torch
     import torch.nn.functional as tf
 
@@ -542,9 +542,16 @@ def collect_ranges(model_or_frozen, x, batch_size: Optional[int] = None) -> Dict
             track(name, net.activation(name))
         for b, srcs in inputs.items():
             a = torch.cat([net.activation(s) for s in srcs], dim=-1).float()
-            c = a.shape[-1]
-            dw = net._dev[f"{b}/dw"].view(3, 3, c).permute(2, 0, 1).reshape(c, 1, 3, 3).contiguous()
-            track(f"{b}/y", tf.conv2d(a.permute(0, 3, 1, 2).contiguous(), dw, padding=1, groups=c))
+            n, h, w, c = a.shape
+            dw = net._dev[f"{b}/dw"].view(3, 3, c).float()
+            # nine taps summed in a fixed order, element by element: the value of a pixel does not
+            # depend on the batch it is in (a library convolution may pick its algorithm, and with it
+            # the summation order, from the batch size)
+            ap = tf.pad(a, (0, 0, 1, 1, 1, 1))
+            y = ap[:, 0:h, 0:w] * dw[0, 0]
+            for t in range(1, 9):
+                y = y + ap[:, t // 3:t // 3 + h, t % 3:t % 3 + w] * dw[t // 3, t % 3]
+            track(f"{b}/y", y)
     net._kept = {}
     return {k: float(v.item()) for k, v in best.items()}
 
