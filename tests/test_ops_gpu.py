@@ -513,9 +513,11 @@ def test_head_dice(ops, ncls, loss_kind):
 def test_head_multiclass_shapes(ops, ncls, cin, mode, nhw, unaligned):
     """Softmax head forward + dice-loss backward (u_net.py:105-112, losses) over class counts that
     round up to every register width (4..32), ragged and multi-tile pixel counts, tiles that span
-    two images (323 pixels an image), the register kernels (Cin <= 64, Cin/4 dividing 256) and the
-    general ones (Cin 48 backward, Cin 128); unaligned: prob and y_true start 4 bytes past a
-    16-byte boundary (the scalar staging / store paths)."""
+    two images (323 pixels an image), and every multi-class route of csrc/head_plan.h.  Forward: MFMA
+    (Cin 16, 64), REG (Cin 4 and 48: Cin <= 64 without the matrix-core shapes), GENERAL (Cin 128).
+    Backward: MC_FUSED (<= 24 classes at Cin 4, 16, 64), MC_REG (32 classes there; Cin 128), GENERAL
+    (Cin 48: Cin / 4 does not divide 256).  unaligned: prob and y_true start 4 bytes past a 16-byte
+    boundary (the scalar staging / store paths)."""
     n, h, w = nhw
     rng = np.random.default_rng(ncls * 131 + cin)
     a, t = _view_inputs(rng, mode, n, h, w, cin)

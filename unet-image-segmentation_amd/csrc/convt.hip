@@ -2,11 +2,8 @@
 // GEMM [M, Cin] x [Cin, 4 Cout] with a pixel-shuffle + bias epilogue, the data gradient a rows
 // GEMM with a pixel-unshuffle A operand, and the kernel gradient a weight-gradient GEMM (gemm.h).
 #include "gemm.h"
+#include "head.h"  // colsum, colsum_workspace
 
-namespace unet {
-int colsum(const float* x, int64_t rows, int cols, float* out, void* ws, size_t ws_bytes, hipStream_t st);
-size_t colsum_workspace(int64_t rows, int cols);
-}  // namespace unet
 using namespace unet;
 
 namespace {

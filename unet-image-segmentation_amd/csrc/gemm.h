@@ -11,7 +11,7 @@
 //   gemm_wgrad (gemm_wgrad.hip) : C[P, Q] = sum_m A[m, P] . B[m, Q]  (weight gradients, reduction over pixels),
 //                split over m into slices; slices are summed in a fixed order (reduce_slabs),
 //                so results are bitwise reproducible.
-//   The entry points that fill RowsArgs / WgradArgs: pointwise.hip, convt.hip, imgblock.hip, head.hip.
+//   The entry points that fill RowsArgs / WgradArgs: pointwise.hip, convt.hip, imgblock.hip, head_bwd.hip.
 //   The tile policy (host only): gemm_plan.h.
 //
 // Tiling (both kernels): 256 threads = 2x2 waves; each wave owns a (BM/2)x(BN/2) block of

@@ -382,7 +382,7 @@ size_t wgrad_workspace(int64_t M, int P, int Q) {
     return align_up((size_t)w.S * P * Q * sizeof(float), 256);
 }
 
-// head dW = sum_m x(m, k) dlogit(m, c): used by head.hip
+// head dW = sum_m x(m, k) dlogit(m, c): used by head_bwd.hip (declared in head.h)
 int head_wgrad(const unet_view* x, int64_t M, const float* dlogit, int ncls, float* dkernel, void* ws, size_t ws_bytes,
                hipStream_t st) {
     WgradArgs a{};
