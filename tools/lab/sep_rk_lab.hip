@@ -57,7 +57,8 @@ static void shape(const char* name, int N, int H, int W, int cin, int cout) {
     old(); CK(hipDeviceSynchronize());
     const double t0 = timeit(old);
     SepArgs b = a; b.y = y1; b.z = z1; b.stats = (float2*)s1;
-    auto rk = [&] { sep::launch_rk(b, MODE, false, true, true, 0); };
+    const sep::SepFwdPlan rkp = sep::sep_fwd_plan(UNET_SEPCONV_RK1, MODE, cin, 0, cout, N, H, W, false, false);
+    auto rk = [&] { sep::launch_rk(b, rkp, MODE, false, true, true, 0); };
     double t2 = 0;
     rk(); CK(hipDeviceSynchronize());
     const double t1 = timeit(rk);

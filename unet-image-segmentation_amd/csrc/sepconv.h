@@ -1,15 +1,16 @@
-// Shared definitions of the fused SeparableConv2D forward kernels (sepconv.hip: the LDS-A-tile
-// schedule; sepconv_rk.hip: the register-A schedule).  Reference model/u_net.py:14-23.
+// Shared definitions of the fused SeparableConv2D forward kernels (sepconv.hip: the entry points, the
+// LDS-A-tile schedule and the pooling-selection pass; sepconv_rk.hip: the register-A schedule, fp32 and
+// split precision; sepconv_px.hip: the persistent split-precision schedule).  Which of them a call runs,
+// and the tile constants, are sepconv_plan.h's.  Reference model/u_net.py:14-23.
 #pragma once
 #include "dispatch.h"
+#include "sepconv_plan.h"
 #include "view.h"
 
 namespace unet {
 namespace sep {
 
-constexpr int TH = 8, TW = 16;            // pixel rectangle of one M tile
-constexpr int HHp = TH + 2, HWp = TW + 2; // halo
-constexpr int BK = 16;                    // channels per k-stage
+constexpr int HHp = TH + 2, HWp = TW + 2;  // halo of one M tile
 enum { E_STORE = 0, E_STATS = 1 };
 
 __device__ __forceinline__ int acc_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
@@ -34,15 +35,17 @@ __device__ __forceinline__ float pool_sel(float a, float b, float c, float d, bo
     return neg ? fminf(fminf(a, b), fminf(c, d)) : fmaxf(fmaxf(a, b), fmaxf(c, d));
 }
 
-// register-A schedule (sepconv_rk.hip): returns 0, or -1 if the mode/shape has no such kernel.
-// With a.pkx (and Cin % 16 == 0, no max-pool view) the split-precision (bf16x6) variant runs.
-int launch_rk(const SepArgs& a, int mode, bool drop, bool stats, bool write_y, hipStream_t st);
-bool rk_x6_supported(int mode, int cin);
-bool rk_supported(int mode, int cin, int cout);
-// persistent split-precision schedule (sepconv_px.hip) for 64 / 128 input and output channels:
-// returns 0, or -1 if the shape has no such kernel (needs a.pkx)
-bool px_supported(const SepArgs& a, int mode, bool all_shapes);
-int launch_px(const SepArgs& a, int mode, bool drop, bool stats, bool write_y, hipStream_t st);
+// ... of four channels at once; n*: the sign of each channel's gamma
+__device__ __forceinline__ float4 pool_sel4(float4 a, float4 b, float4 c, float4 d, bool nx, bool ny, bool nz, bool nw) {
+    return make_float4(pool_sel(a.x, b.x, c.x, d.x, nx), pool_sel(a.y, b.y, c.y, d.y, ny), pool_sel(a.z, b.z, c.z, d.z, nz),
+                       pool_sel(a.w, b.w, c.w, d.w, nw));
+}
+
+// The launchers turn the plan's route, tile width and grid into template arguments; the caller checks the launch.
+// register-A schedule (sepconv_rk.hip), routes SEP_RK and SEP_RK_X6 (split precision, reads a.pkx)
+void launch_rk(const SepArgs& a, const SepFwdPlan& p, int mode, bool drop, bool stats, bool write_y, hipStream_t st);
+// persistent split-precision schedule (sepconv_px.hip), route SEP_PX (reads a.pkx)
+void launch_px(const SepArgs& a, const SepFwdPlan& p, int mode, bool drop, bool stats, bool write_y, hipStream_t st);
 
 }  // namespace sep
 }  // namespace unet

@@ -337,56 +337,23 @@ __global__ __launch_bounds__(128 * WN, sep_min_waves(BN, WN)) void sepconv_fwd_k
     }
 }
 
-int launch(const SepArgs& a, int mode, bool drop, bool stats, bool write_y, hipStream_t st) {
-    // the 256-wide, 8-wave tile when it still gives every CU (256) a block; else 128 (measured:
-    // tools/bench_sepconv.py, profiles/r1i_sepconv_bn_sweep.log)
-    const int64_t mt = (int64_t)a.N * (a.H / TH) * (a.W / TW);
-    int bn = a.Cout <= 64 ? 64 : a.Cout <= 128 ? 128 : 256;
-    if (bn == 256 && mt * cdiv(a.Cout, 256) < 256) bn = 128;
-    const dim3 grid((unsigned)mt, (unsigned)cdiv(a.Cout, bn));
+// route SEP_TILE: the plan's tile width and grid as template arguments
+void launch_tile(const SepArgs& a, const SepFwdPlan& p, int mode, bool drop, bool stats, bool write_y, hipStream_t st) {
+    const dim3 grid(p.grid_x, p.grid_y);
     with_view(mode, drop, [&](auto M, auto D) {
-        with_int<64, 128, 256>(bn, [&](auto BN) {
+        with_int<64, 128, 256>(p.bn, [&](auto BN) {
             constexpr int WN = BN() == 256 ? 4 : 2;  // waves along N
             with_bool(stats, [&](auto S) {
                 with_bool(write_y, [&](auto WY) {
                     sepconv_fwd_kernel<M(), D(), S() ? E_STATS : E_STORE, BN(), WN, WY()>
-                        <<<grid, 128 * WN, 0, st>>>(a);
+                        <<<grid, p.threads, 0, st>>>(a);
                 });
             });
         });
     });
-    UNET_CHECK_LAUNCH("unet_sepconv_fwd");
-    return 0;
 }
 
-}  // namespace
-}  // namespace unet
-
-using namespace unet;
-
-namespace {
-int g_sep_schedule = UNET_SEPCONV_AUTO;
-}
-
-extern "C" int unet_sepconv_set_schedule(int schedule) {
-    UNET_CHECK_ARG(schedule >= UNET_SEPCONV_AUTO && schedule <= UNET_SEPCONV_RK1, "unet_sepconv_set_schedule: bad value");
-    const int old = g_sep_schedule;
-    g_sep_schedule = schedule;
-    return old;
-}
-
-extern "C" int unet_sepconv_fwd_supported(const unet_view* x, int n, int h, int w, int cout) {
-    if (!x || n <= 0 || h <= 0 || w <= 0 || cout <= 0) return 0;
-    const int C = x->c0 + (x->mode == UNET_VIEW_CONCAT ? x->c1 : 0);
-    if (h % TH || w % TW || C % 4 || cout % 4) return 0;
-    if (x->mode == UNET_VIEW_CONCAT && x->c0 % 4) return 0;
-    const int64_t M = (int64_t)n * h * w;
-    return M * C < (int64_t(1) << 31) && M * cout < (int64_t(1) << 31) &&
-           (int64_t)n * h * w * C * (x->mode == UNET_VIEW_POOL_BNRELU ? 4 : 1) < (int64_t(1) << 31);
-}
-
-namespace unet {
-namespace {
+// The pooling selection as a pass of its own (unet_pool_select; after the kernel of route SEP_TILE):
 // zsel[n][i][j][c] = pool_sel over z's 2x2 window (2i..2i+1, 2j..2j+1), channel quads
 __global__ __launch_bounds__(256) void pool_select_kernel(const float* __restrict__ z, int64_t quads, int H2, int W2,
                                                           int C, const float* __restrict__ gamma, float* __restrict__ out) {
@@ -400,16 +367,28 @@ __global__ __launch_bounds__(256) void pool_select_kernel(const float* __restric
         const float* b = z + r0 * C + 4 * q;
         const float4 a = ld4(b), bb = ld4(b + C), c = ld4(b + 2 * W2 * C), d = ld4(b + 2 * W2 * C + C);
         const float4 gm = gamma ? ld4(gamma + 4 * q) : f4(0.f);
-        float4 o;
-        o.x = sep::pool_sel(a.x, bb.x, c.x, d.x, signbit(gm.x));
-        o.y = sep::pool_sel(a.y, bb.y, c.y, d.y, signbit(gm.y));
-        o.z = sep::pool_sel(a.z, bb.z, c.z, d.z, signbit(gm.z));
-        o.w = sep::pool_sel(a.w, bb.w, c.w, d.w, signbit(gm.w));
+        const float4 o = sep::pool_sel4(a, bb, c, d, signbit(gm.x), signbit(gm.y), signbit(gm.z), signbit(gm.w));
         st4(out + p * C + 4 * q, o);
     }
 }
+
+int g_sep_schedule = UNET_SEPCONV_AUTO;
+
 }  // namespace
 }  // namespace unet
+
+using namespace unet;
+
+extern "C" int unet_sepconv_set_schedule(int schedule) {
+    UNET_CHECK_ARG(schedule >= UNET_SEPCONV_AUTO && schedule <= UNET_SEPCONV_RK1, "unet_sepconv_set_schedule: bad value");
+    const int old = g_sep_schedule;
+    g_sep_schedule = schedule;
+    return old;
+}
+
+extern "C" int unet_sepconv_fwd_supported(const unet_view* x, int n, int h, int w, int cout) {
+    return x && sep_fwd_supported(x->mode, x->c0, x->c1, n, h, w, cout);
+}
 
 extern "C" int unet_pool_select(const float* z, int n, int h, int w, int c, const float* gamma, float* out,
                                 unet_stream_t stream) {
@@ -431,6 +410,16 @@ extern "C" int unet_sepconv_fwd(const unet_view* x, int n, int h, int w, const f
     UNET_CHECK_ARG(unet_sepconv_fwd_supported(x, n, h, w, cout),
                    "unet_sepconv_fwd: unsupported shape (needs h%%8==0, w%%16==0, channels%%4==0)");
     UNET_CHECK_ARG(dw_kernel && pw_kernel && z, "unet_sepconv_fwd: null pointer");
+    // (z too: the selection may be a pass over z after the kernel, and no launch precedes a refusal)
+    UNET_CHECK_ARG(!z_pool_sel || (h % 2 == 0 && w % 2 == 0 &&
+                                   ((uintptr_t)z_pool_sel | (uintptr_t)gamma | (uintptr_t)z) % 16 == 0),
+                   "unet_sepconv_fwd: z_pool_sel needs even h, w and 16-B aligned buffers");
+    UNET_CHECK_ARG(((uintptr_t)pw_kernel_x3 & 15) == 0, "unet_sepconv_fwd: pw_kernel_x3 must be 16-B aligned");
+    // register-A schedule where it exists unless the LDS-A-tile schedule is forced, the persistent kernel for
+    // the short-K shapes unless the one-tile-per-block kernel is forced: sepconv_plan.h
+    const SepFwdPlan p = sep_fwd_plan(g_sep_schedule, x->mode, x->c0, x->c1, cout, n, h, w, pw_kernel_x3 != nullptr,
+                                      z_pool_sel != nullptr);
+    UNET_CHECK_ARG(p.route != SEP_REFUSED, "unet_sepconv_fwd: no register-A kernel for this view / shape");
     SepArgs a{};
     a.x = make_dview(*x);
     a.N = n;
@@ -445,36 +434,16 @@ extern "C" int unet_sepconv_fwd(const unet_view* x, int n, int h, int w, const f
     a.stats = reinterpret_cast<float2*>(bn_partials);
     const bool stats = bn_partials != nullptr, wy = y != nullptr, drop = x->drop_rate > 0.f;
     hipStream_t st = as_stream(stream);
-    if (z_pool_sel) {
-        UNET_CHECK_ARG(h % 2 == 0 && w % 2 == 0 && ((uintptr_t)z_pool_sel | (uintptr_t)gamma) % 16 == 0,
-                       "unet_sepconv_fwd: z_pool_sel needs even h, w and 16-B aligned buffers");
-    }
-    if (z_pool_sel && !(g_sep_schedule != UNET_SEPCONV_TILE && rk_supported(x->mode, a.Cin, cout))) {
-        // LDS-A-tile schedule: the selection in a pass over z after the kernel
-        const int rc = unet_sepconv_fwd(x, n, h, w, dw_kernel, cout, pw_kernel, pw_kernel_x3, y, z, bn_partials,
-                                        nullptr, nullptr, stream);
-        return rc ? rc : unet_pool_select(z, n, h, w, cout, gamma, z_pool_sel, stream);
-    }
-    a.zsel = z_pool_sel;
-    a.gamma = gamma;
-    UNET_CHECK_ARG(((uintptr_t)pw_kernel_x3 & 15) == 0, "unet_sepconv_fwd: pw_kernel_x3 must be 16-B aligned");
     a.pkx = pw_kernel_x3;
-    // register-A schedule where it exists (rk_supported: BN+ReLU / concat / plain views of >= 64
-    // channels, max-pool views of >= 64 inputs and <= 128 outputs) unless the LDS-A-tile schedule
-    // is forced; wider max-pool views keep the LDS-A-tile kernel (its 256-wide 8-wave tile pools
-    // each halo element once for all columns)
-    if (g_sep_schedule != UNET_SEPCONV_TILE && rk_supported(x->mode, a.Cin, cout)) {
-        // the persistent split-precision kernel for the short-K shapes (sepconv_px.hip), unless
-        // the one-tile-per-block register-A kernel is forced
-        if (g_sep_schedule != UNET_SEPCONV_RK1 && px_supported(a, x->mode, g_sep_schedule == UNET_SEPCONV_RK)) {
-            if (launch_px(a, x->mode, drop, stats, wy, st)) return -1;
-            UNET_CHECK_LAUNCH("unet_sepconv_fwd");
-            return 0;
-        }
-        if (launch_rk(a, x->mode, drop, stats, wy, st)) return -1;
-        UNET_CHECK_LAUNCH("unet_sepconv_fwd");
-        return 0;
+    if (!p.pool_pass) {  // the kernel's own epilogue writes the selection
+        a.zsel = z_pool_sel;
+        a.gamma = gamma;
     }
-    UNET_CHECK_ARG(g_sep_schedule != UNET_SEPCONV_RK, "unet_sepconv_fwd: no register-A kernel for this view / shape");
-    return launch(a, x->mode, drop, stats, wy, st);
+    switch (p.route) {
+        case SEP_TILE: launch_tile(a, p, x->mode, drop, stats, wy, st); break;
+        case SEP_PX: launch_px(a, p, x->mode, drop, stats, wy, st); break;
+        default: launch_rk(a, p, x->mode, drop, stats, wy, st);
+    }
+    UNET_CHECK_LAUNCH("unet_sepconv_fwd");
+    return p.pool_pass ? unet_pool_select(z, n, h, w, cout, gamma, z_pool_sel, stream) : 0;
 }

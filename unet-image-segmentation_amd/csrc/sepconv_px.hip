@@ -313,11 +313,7 @@ __global__ __launch_bounds__(256, 2) void sepconv_px_kernel(SepArgs g, int ntile
                 const float4 d = *reinterpret_cast<const float4*>(T + (16 + ((c1 + 2) & 15)) * PTLD + 4 * qd);
                 const int col = cb + 4 * qd;
                 const unsigned gb = gneg >> (4 * tn);
-                float4 o;
-                o.x = pool_sel(a.x, b.x, c.x, d.x, (gb & 1u) != 0);
-                o.y = pool_sel(a.y, b.y, c.y, d.y, (gb & 2u) != 0);
-                o.z = pool_sel(a.z, b.z, c.z, d.z, (gb & 4u) != 0);
-                o.w = pool_sel(a.w, b.w, c.w, d.w, (gb & 8u) != 0);
+                const float4 o = pool_sel4(a, b, c, d, (gb & 1u) != 0, (gb & 2u) != 0, (gb & 4u) != 0, (gb & 8u) != 0);
                 const int H2 = g.H >> 1, W2 = g.W >> 1;
                 st4(g.zsel + ((int64_t)(n * H2 + (h0 >> 1) + wave) * W2 + (w0 >> 1) + j) * g.Cout + col, o);
             }
@@ -388,38 +384,16 @@ __global__ __launch_bounds__(256, 2) void sepconv_px_kernel(SepArgs g, int ntile
 
 }  // namespace
 
-bool px_supported(const SepArgs& a, int mode, bool all_shapes) {
-    if (!a.pkx || lab_knob("UNET_PX", 1) == 0) return false;  // (lab: UNET_PX=0 keeps the one-tile kernel)
-    if (mode != UNET_VIEW_PLAIN && mode != UNET_VIEW_BNRELU && mode != UNET_VIEW_CONCAT) return false;
-    if ((a.Cin != 64 && a.Cin != 128) || (a.Cout != 64 && a.Cout != 128)) return false;
-    // Only the shapes where it wins INSIDE the train step: 128 outputs from 64 inputs or with the
-    // pool-selection epilogue (enc2_block1 79.0 -> 78.2 us, enc2_block2 147.2 -> 138.8 us).  Isolated
-    // on a repeated input it also beats the one-tile kernel on 64 -> 64 (1.09-1.14x,
-    // profiles/r4l_px_lab.log), but in the step enc1_block2 165 -> 173, dec1_block2 137 -> 158,
-    // dec1_block1 258 -> 265, dec2_block2 133 -> 136 us (profiles/r4q_px_in_step.txt).
-    // all_shapes (schedule RK) or UNET_PX_ALL=1 (lab) take every supported shape.
-    if (!all_shapes && lab_knob("UNET_PX_ALL", 0) == 0 && !(a.Cout == 128 && (a.Cin == 64 || a.zsel))) return false;
-    if (mode == UNET_VIEW_CONCAT && a.x.c0 % 16) return false;
-    return a.H % TH == 0 && a.W % TW == 0;
-}
-
-int launch_px(const SepArgs& a, int mode, bool drop, bool stats, bool write_y, hipStream_t st) {
-    if (!px_supported(a, mode, true)) return -1;
-    const int ntiles = a.N * (a.H / TH) * (a.W / TW);
-    // two blocks per CU; equal runs of tiles (the grid is the tile count / the tiles per block)
-    const int slots = 256 * lab_knob("UNET_PX_BPC", 2);
-    const int per = (ntiles + slots - 1) / slots;
-    const int grid = (ntiles + per - 1) / per;
-    const int pd = lab_knob("UNET_PX_PD", 2);
+void launch_px(const SepArgs& a, const SepFwdPlan& p, int mode, bool drop, bool stats, bool write_y, hipStream_t st) {
     auto launch = [&](auto PD) {  // PD: the prefetch depth
         with_int<UNET_VIEW_PLAIN, UNET_VIEW_BNRELU, UNET_VIEW_CONCAT>(mode, [&](auto M) {
             with_bool(drop, [&](auto D) {
-                with_int<64, 128>(a.Cout, [&](auto BN) {
+                with_int<64, 128>(p.bn, [&](auto BN) {
                     with_int<64, 128>(a.Cin, [&](auto CIN) {
                         with_bool(stats, [&](auto S) {
                             with_bool(write_y, [&](auto WY) {
                                 sepconv_px_kernel<M(), D(), S(), BN(), CIN(), WY(), PD()>
-                                    <<<grid, 256, 0, st>>>(a, ntiles);
+                                    <<<p.grid_x, p.threads, 0, st>>>(a, p.ntiles);
                             });
                         });
                     });
@@ -428,12 +402,10 @@ int launch_px(const SepArgs& a, int mode, bool drop, bool stats, bool write_y, h
         });
     };
 #ifdef UNET_LAB_BUILD  // other prefetch depths: lab only (UNET_PX_PD=1, 3, 4)
-    with_int<1, 3, 4, 2>(pd, launch);
+    with_int<1, 3, 4, 2>(p.pd, launch);
 #else
-    (void)pd;
     launch(Int<2>{});
 #endif
-    return 0;
 }
 
 }  // namespace sep

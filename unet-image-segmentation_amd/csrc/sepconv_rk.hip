@@ -470,11 +470,7 @@ __global__ __launch_bounds__(256, X6 && BN <= 128 ? 3 : 2) void sepconv_rk_kerne
                 const int col = cbase + 4 * q;
                 if (col < g.Cout) {
                     const float4 gm = g.gamma ? ld4(g.gamma + col) : f4(0.f);
-                    float4 o;
-                    o.x = pool_sel(a.x, b.x, c.x, d.x, signbit(gm.x));
-                    o.y = pool_sel(a.y, b.y, c.y, d.y, signbit(gm.y));
-                    o.z = pool_sel(a.z, b.z, c.z, d.z, signbit(gm.z));
-                    o.w = pool_sel(a.w, b.w, c.w, d.w, signbit(gm.w));
+                    const float4 o = pool_sel4(a, b, c, d, signbit(gm.x), signbit(gm.y), signbit(gm.z), signbit(gm.w));
                     const int H2 = g.H >> 1, W2 = g.W >> 1;
                     st4(g.zsel + ((int64_t)(n * H2 + (h0 >> 1) + wave) * W2 + (w0 >> 1) + j) * g.Cout + col, o);
                 }
@@ -493,40 +489,23 @@ __global__ __launch_bounds__(256, X6 && BN <= 128 ? 3 : 2) void sepconv_rk_kerne
 
 }  // namespace
 
-bool rk_x6_supported(int mode, int cin) { return mode != UNET_VIEW_POOL_BNRELU && cin % 16 == 0 && cin >= 64; }
-
-bool rk_supported(int mode, int cin, int cout) {
-    // max-pool views only up to 128 output channels: wider layers keep the LDS-A-tile kernel's
-    // 256-wide 8-wave tile, which pools each halo element once for all columns (measured:
-    // tools/lab/sep_rk_lab.hip, enc3_block1 / enc4_block1)
-    return mode >= UNET_VIEW_PLAIN && mode <= UNET_VIEW_CONCAT && cin >= 64 && cout >= 64 &&
-           (mode != UNET_VIEW_POOL_BNRELU || cout <= 128);
-}
-
-int launch_rk(const SepArgs& a, int mode, bool drop, bool stats, bool write_y, hipStream_t st) {
-    if (!rk_supported(mode, a.Cin, a.Cout)) return -1;
-    // split precision with >= 256 outputs: one 256-column tile (two blocks per CU), so the
-    // depthwise and its halo are evaluated once per pixel tile instead of once per 128 columns,
-    // and the 64 x 64 level's 512 pixel tiles fill the 512 block slots in one round
-    const bool x6 = a.pkx && rk_x6_supported(mode, a.Cin);
-    const int bn = a.Cout <= 64 ? 64 : (x6 && a.Cout >= 256 ? 256 : 128);
-    const dim3 grid((unsigned)(a.N * (a.H / TH) * (a.W / TW)), (unsigned)cdiv(a.Cout, bn));
+void launch_rk(const SepArgs& a, const SepFwdPlan& p, int mode, bool drop, bool stats, bool write_y, hipStream_t st) {
+    const dim3 grid(p.grid_x, p.grid_y);
     with_view(mode, drop, [&](auto M, auto D) {
-        with_int<64, 128, 256>(bn, [&](auto BN) {
-            with_bool(x6, [&](auto X6) {
+        with_int<64, 128, 256>(p.bn, [&](auto BN) {
+            with_bool(p.route == SEP_RK_X6, [&](auto X6) {
                 // no split-precision kernel for the max-pool view, and the 256-column tile only with it
                 if constexpr (X6() ? M() != UNET_VIEW_POOL_BNRELU : BN() != 256) {
                     with_bool(stats, [&](auto S) {
                         with_bool(write_y, [&](auto WY) {
                             sepconv_rk_kernel<M(), D(), S() ? E_STATS : E_STORE, BN(), WY(), X6()>
-                                <<<grid, 256, 0, st>>>(a);
+                                <<<grid, p.threads, 0, st>>>(a);
                         });
                     });
                 }
             });
         });
     });
-    return 0;
 }
 
 }  // namespace sep

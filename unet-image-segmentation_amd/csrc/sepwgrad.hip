@@ -15,6 +15,7 @@
 // tiles, one fixed-order slab per block, reduced by reduce_slabs in fixed order.
 #include "common.h"
 #include "dispatch.h"
+#include "sepconv_plan.h"
 #include "view.h"
 
 namespace unet {
@@ -24,8 +25,6 @@ namespace {
                // 4 loads of the next tile, 8 LDS staging, 16 the dy MFMA, 32 the dy store
 #define SW_KO 0
 #endif
-constexpr int TH = 8, TW = 16;  // shape granularity of the C-ABI (h % 8, w % 16)
-constexpr int CI = 64;          // input channels per block (ci group)
 __device__ __forceinline__ int acc_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 struct SwArgs {
@@ -60,9 +59,9 @@ struct SwArgs {
 // this form: enc1_block2 320 -> 307 us, dec1_block1 597 -> 532 us, step +1.2 %).
 // A block walks its run of tiles down a column (th fastest): consecutive tiles share two halo rows.
 namespace fb {
-constexpr int TH = 4, TW = 16, HWp = TW + 2, HPIX = (TH + 2) * HWp;  // 108 halo pixels
+constexpr int TH = sep::BTH, TW = sep::BTW, HWp = TW + 2, HPIX = (TH + 2) * HWp;  // 4 x 16 tile, 108 halo pixels
 constexpr int PX = TH * TW;                                          // 64 pixels per tile
-constexpr int NT = 256, CI = 64, CO = 64, ZS = CO + 1;
+constexpr int NT = 256, CI = sep::CI, CO = 64, ZS = CO + 1;
 constexpr int NHQ = HPIX * (CI / 4);    // halo float4 (1728)
 constexpr int HR = (NHQ + NT - 1) / NT;  // per thread (7)
 constexpr int DQ = PX * (CO / 4) / NT;   // dz float4 per thread (4)
@@ -468,55 +467,27 @@ int resident_cus() {
     return cus;
 }
 
-struct SwPlan {
-    int tiles, ncig, S, tps;
-};
-SwPlan sw_plan(int n, int h, int w, int cin) {
-    SwPlan p;
-    p.tiles = n * (h / fb::TH) * (w / fb::TW);
-    p.ncig = cin / CI;
-    // two blocks per CU (77 KB of LDS each), m-slices a multiple of 8 (the XCD map).  (Fewer blocks,
-    // leaving CUs to the main stream: -1.7 / -0.3 % img/s in round 2; 2-8x as many, finer runs:
-    // no gain, profiles/r3m_fb_split_ab.log.)
-    int S = (int)cdiv(2 * resident_cus(), p.ncig);
-    S = (int)cdiv(S, 8) * 8;
-    p.tps = (int)cdiv(p.tiles, S);
-    p.S = S;
-    return p;
-}
-
 }  // namespace
 }  // namespace unet
 
 using namespace unet;
 
 extern "C" int unet_sepconv_bwd_filter_supported(const unet_view* x, int n, int h, int w, int cout) {
-    // 64 outputs (the 256 x 256 level) or 128 (the 128 x 128 level: 142 KB of LDS; isolated it is
-    // slower than the separate launches, 224 vs 188 us in tools/bench_sepwgrad.py, but it lets the
-    // forward skip the y store -- the engine chooses per level)
-    if (!x || n <= 0 || h <= 0 || w <= 0 || (cout != 64 && cout != 128)) return 0;
-    if (x->mode != UNET_VIEW_PLAIN && x->mode != UNET_VIEW_BNRELU && x->mode != UNET_VIEW_CONCAT) return 0;
-    const int C = x->c0 + (x->mode == UNET_VIEW_CONCAT ? x->c1 : 0);
-    if (C % CI || h % TH || w % TW) return 0;
-    if (x->mode == UNET_VIEW_CONCAT && x->c0 % 4) return 0;
-    const int64_t M = (int64_t)n * h * w;
-    return M * C < (int64_t(1) << 31) && M * cout < (int64_t(1) << 31);
+    return x && sep::sep_bwd_supported(x->mode, x->c0, x->c1, n, h, w, cout);
 }
 
 extern "C" size_t unet_sepconv_bwd_filter_workspace(int n, int h, int w, int cin, int cout) {
-    if (n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cin % CI || (cout != 64 && cout != 128) || h % TH || w % TW)
-        return 0;
-    const SwPlan p = sw_plan(n, h, w, cin);
-    return align_up((size_t)p.S * cin * cout * sizeof(float), 256) + align_up((size_t)p.S * 9 * cin * sizeof(float), 256);
+    // 0 where no view of cin channels is supported
+    if (!sep::sep_bwd_supported(UNET_VIEW_PLAIN, cin, 0, n, h, w, cout)) return 0;
+    return sep::sep_bwd_plan(n, h, w, cin, cout, resident_cus()).bytes;
 }
 
 namespace {
 int run_sw(const unet_view* x, int n, int h, int w, const float* dw_kernel, SwArgs a, int cout, float* d_dw_kernel,
            float* d_pw_kernel, void* ws, size_t ws_bytes, unet_stream_t stream, const char* op) {
-    const int cin = x->c0 + (x->mode == UNET_VIEW_CONCAT ? x->c1 : 0);
-    const size_t need = unet_sepconv_bwd_filter_workspace(n, h, w, cin, cout);
-    UNET_CHECK_ARG(ws && ws_bytes >= need, "%s: workspace %zu < %zu", op, ws_bytes, need);
-    const SwPlan p = sw_plan(n, h, w, cin);
+    const int cin = sep::view_channels(x->mode, x->c0, x->c1);
+    const sep::SepBwdPlan p = sep::sep_bwd_plan(n, h, w, cin, cout, resident_cus());
+    UNET_CHECK_ARG(ws && ws_bytes >= p.bytes, "%s: workspace %zu < %zu", op, ws_bytes, p.bytes);
     a.x = make_dview(*x);
     a.N = n;
     a.H = h;
@@ -524,22 +495,21 @@ int run_sw(const unet_view* x, int n, int h, int w, const float* dw_kernel, SwAr
     a.Cin = cin;
     a.dk = dw_kernel;
     a.pw_slab = static_cast<float*>(ws);
-    a.dw_slab = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up((size_t)p.S * cin * cout * sizeof(float), 256));
+    a.dw_slab = reinterpret_cast<float*>(static_cast<char*>(ws) + p.dw_slab_off);
     a.tiles = p.tiles;
     a.tps = p.tps;
     a.ncig = p.ncig;
-    const int blocks = p.S * p.ncig;
     hipStream_t st = as_stream(stream);
     const bool drop = x->drop_rate > 0.f;
     with_int<UNET_VIEW_PLAIN, UNET_VIEW_BNRELU, UNET_VIEW_CONCAT>(x->mode, [&](auto M) {
         if (a.da_dl) {
-            sepconv_bwd_fused_kernel<M(), true><<<blocks, fb::NT, 0, st>>>(a);
+            sepconv_bwd_fused_kernel<M(), true><<<p.blocks, fb::NT, 0, st>>>(a);
         } else if (a.da) {
-            sepconv_bwd_fused_kernel<M()><<<blocks, fb::NT, 0, st>>>(a);
+            sepconv_bwd_fused_kernel<M()><<<p.blocks, fb::NT, 0, st>>>(a);
         } else {
             with_bool(drop, [&](auto D) {
                 with_int<128, 64>(cout, [&](auto CO) {
-                    sepconv_bwd_filter2_kernel<M(), D(), CO()><<<blocks, fb::NT, 0, st>>>(a);
+                    sepconv_bwd_filter2_kernel<M(), D(), CO()><<<p.blocks, fb::NT, 0, st>>>(a);
                 });
             });
         }
