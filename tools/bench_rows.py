@@ -4,6 +4,9 @@ float64 product on the device, for the three rows-GEMM ops of the train step at 
 the BatchNorm-backward data gradient (the step's dominant op) and the Conv2DTranspose forward.
 
     UNET_HIP_LIB=tools/labbin/libunet_hip_lab.so UNET_X6=1 python tools/bench_rows.py TAG
+
+UNET_X6 (default 1) also decides whether the ops get the weights' split-precision planes, as the
+engine hands them: without planes every shape takes the fp32 route, in any library.
 """
 import json
 import os
@@ -19,6 +22,17 @@ PEAK = 157.3
 B = int(os.environ.get("B", 16))
 TAG = sys.argv[1] if len(sys.argv) > 1 else os.environ.get("UNET_X6", "0")
 dev = "cuda"
+PLANES = os.environ.get("UNET_X6", "1") != "0"
+
+
+def planes(w2d, keep):
+    """bf16 x 3 planes of a (rows, cols) weight matrix (ops.split_x3), or None when UNET_X6=0."""
+    if not PLANES:
+        return None
+    rows, cols = w2d.shape
+    t = torch.empty(3 * rows * cols, dtype=torch.int16, device=dev)
+    ops.split_x3(w2d.contiguous().reshape(-1), [(0, rows, cols, 0)], t, keep=keep)
+    return t
 DGRAD = [("enc1_block2", 256, 64, 64), ("enc2_block1", 128, 64, 128), ("enc2_block2", 128, 128, 128),
          ("enc3_block1", 64, 128, 256), ("enc3_block2", 64, 256, 256), ("enc4_block1", 32, 256, 512),
          ("enc4_block2", 32, 512, 512), ("bneck_block1", 16, 512, 1024), ("dec4_block2", 32, 512, 512),
@@ -67,7 +81,8 @@ def main():
         coef = (torch.randn(3 * cout, generator=g) * 0.1).to(dev)
         dy = torch.empty(m, cin, device=dev)
         dz = torch.empty(m, cout, device=dev)
-        s = bench(lambda: ops.pointwise_bwd_data_bnrelu(da, z, m, cin, cout, pk, sc, sh, coef, 0.0, 7, dy, dz))
+        pkd = planes(pk, keep=True)
+        s = bench(lambda: ops.pointwise_bwd_data_bnrelu(da, z, m, cin, cout, pk, sc, sh, coef, 0.0, 7, dy, dz, pkd=pkd))
         err = rel(dy, dz.double() @ pk.double().T)
         t = emit("dgrad_bnrelu", name, m, cout, cin, s, 2.0 * m * cin * cout, err)
         tot.setdefault("dgrad_bnrelu", []).append(t)
@@ -78,7 +93,8 @@ def main():
         pk = (torch.randn(cin, cout, generator=g) / cin ** 0.5).to(dev)
         z = torch.empty(m, cout, device=dev)
         part = torch.zeros(ops.bn_partials_numel(m, cout), device=dev)
-        s = bench(lambda: ops.pointwise_fwd(y, m, cin, cout, pk, z, part))
+        pkx = planes(pk, keep=False)
+        s = bench(lambda: ops.pointwise_fwd(y, m, cin, cout, pk, z, part, pkx=pkx))
         err = rel(z, y.double() @ pk.double())
         tot.setdefault("pointwise_fwd", []).append(emit("pointwise_fwd", name, m, cin, cout, s, 2.0 * m * cin * cout,
                                                          err))
@@ -90,7 +106,8 @@ def main():
         b = torch.randn(cout, generator=g).to(dev)
         out = torch.empty(B, 2 * hw, 2 * hw, cout, device=dev)
         v = View.plain(x)
-        s = bench(lambda: ops.conv_transpose2x2_fwd(v, B, hw, hw, cout, k, b, out))
+        kx = planes(k.reshape(4 * cout, cin), keep=True)
+        s = bench(lambda: ops.conv_transpose2x2_fwd(v, B, hw, hw, cout, k, b, out, kx=kx))
         ref = torch.einsum("nijc,abdc->niajbd", x.double(), k.double()).reshape(B, 2 * hw, 2 * hw, cout) + b.double()
         err = rel(out, ref)
         tot.setdefault("convT_fwd", []).append(emit("convT_fwd", name, m, cin, 4 * cout, s, 8.0 * m * cin * cout, err))

@@ -1,6 +1,8 @@
 // The rows GEMM C[M, N] = A[M, K] . B[K, N] (see gemm.h): the scalar fall-back kernel, the
 // vectorised kernel (fp32 and split-precision bf16x6 "X6" k-loops, four epilogues), and
 // launch_rows, which picks the tile (gemm_plan.h) and the kernel.
+#include <type_traits>
+
 #include "dispatch.h"
 #include "gemm.h"
 
@@ -238,6 +240,32 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(RowsArgs g) {
 __device__ unsigned long long lab_rows_stamps[65536 * 4];  // ROWS_STAMP (gemm.h): [block][4]
 #endif
 
+// The split-precision k-loop's form of UNET_BN_BWD_DZ4 (common.h), with the one contraction the
+// expression allows written out: dz = sc * (g - p - (z - mu) * q) either rounds the product and
+// subtracts (FUSE = false) or takes one fma (FUSE = true).  Under -ffp-contract=fast the compiler
+// chose per inlined copy of store_stage -- separate rounding for stage 0, fma inside the loop -- and
+// a restructured loop flipped the choice, which changes dz and dy bits (tests/test_rows_bits_gpu.py
+// holds them).  The call sites now name the form; the results are those of that earlier code.
+template <bool FUSE>
+__device__ __forceinline__ float bn_bwd_dz_as(float g, float z, float sc, float sh, float mu, float p, float q) {
+    g = fmaf(z, sc, sh) > 0.f ? g : 0.f;
+    if constexpr (FUSE) {
+        return sc * fmaf(-(z - mu), q, g - p);
+    } else {
+        float t = (z - mu) * q;
+        asm("" : "+v"(t));  // (the rounded product: -ffp-contract=fast fuses across anything less)
+        return sc * ((g - p) - t);
+    }
+}
+template <bool FUSE>
+__device__ __forceinline__ float4 bn_bwd_dz4_as(float4 g, float4 z, float4 sc, float4 sh, float4 mu, float4 p,
+                                                float4 q) {
+    return make_float4(bn_bwd_dz_as<FUSE>(g.x, z.x, sc.x, sh.x, mu.x, p.x, q.x),
+                       bn_bwd_dz_as<FUSE>(g.y, z.y, sc.y, sh.y, mu.y, p.y, q.y),
+                       bn_bwd_dz_as<FUSE>(g.z, z.z, sc.z, sh.z, mu.z, p.z, q.z),
+                       bn_bwd_dz_as<FUSE>(g.w, z.w, sc.w, sh.w, mu.w, p.w, q.w));
+}
+
 template <int BM, int BN, int BK, int AMODE, bool DROP, int EPI, bool BKC, bool X6 = false>
 __global__ __launch_bounds__(256, X6 ? 2 : 1) void gemm_rows_vec(RowsArgs g) {
     main_stream_prio();
@@ -376,7 +404,7 @@ __global__ __launch_bounds__(256, X6 ? 2 : 1) void gemm_rows_vec(RowsArgs g) {
         }
         }
     };
-    auto store_stage = [&](int buf) {
+    auto store_stage = [&](int buf, auto fuse) {
         const bool kv = ak < K;
         if constexpr (XCOEF) {  // (ak < K on this route: K % 32 == 0)
             csc = *reinterpret_cast<const float4*>(xcoef + ak);
@@ -395,7 +423,11 @@ __global__ __launch_bounds__(256, X6 ? 2 : 1) void gemm_rows_vec(RowsArgs g) {
             }
             if constexpr (AMODE == A_BNBWD) {
                 const float4 zz = rz[r];
-                UNET_BN_BWD_DZ4(v, zz, csc, csh, cmu, cp, cq);  // (as text: see common.h)
+                if constexpr (X6) {
+                    v = bn_bwd_dz4_as<decltype(fuse)::value>(v, zz, csc, csh, cmu, cp, cq);
+                } else {
+                    UNET_BN_BWD_DZ4(v, zz, csc, csh, cmu, cp, cq);  // (as text: see common.h)
+                }
             }
             if (!kv || aoff[r] < 0) v = f4(0.f);
             if constexpr (AMODE == A_BNBWD) {
@@ -449,13 +481,11 @@ __global__ __launch_bounds__(256, X6 ? 2 : 1) void gemm_rows_vec(RowsArgs g) {
     }
     load_stage(0);
     if constexpr (XCOEF) __syncthreads();
-    store_stage(0);
+    store_stage(0, std::false_type{});
     __syncthreads();
     ROWS_STAMP(g, 1);
-    for (int kt = 0; kt < nk; ++kt) {
-        const int buf = kt & 1;
-        if (kt + 1 < nk) load_stage((kt + 1) * BK);
-        if constexpr (X6) {
+    if constexpr (X6) {
+        auto mfma_stage = [&]() {
 #pragma unroll
             for (int ks = 0; ks < BK / 16; ++ks) {
                 // the wave's B fragments for this 16-deep step, then one row tile's A fragments at a
@@ -478,14 +508,29 @@ __global__ __launch_bounds__(256, X6 ? 2 : 1) void gemm_rows_vec(RowsArgs g) {
                     for (int tn = 0; tn < TN; ++tn) acc[tm][tn] = mfma_x6(af, bfr[tn], acc[tm][tn]);
                 }
             }
+        };
+        // The last stage is peeled off, so load_stage is unconditional inside the loop and the staged
+        // registers live from the loads to the store phase of the SAME iteration.  Under
+        // `if (kt + 1 < nk) load_stage(..)` they are carried around the loop instead, and the
+        // compiler copies them to the carried set right behind the loads: a wait for the whole
+        // prefetch in front of the stage's MFMAs (tools/kloop_waits.py checks it).
+        for (int kt = 0; kt + 1 < nk; ++kt) {
+            load_stage((kt + 1) * BK);
+            __builtin_amdgcn_sched_barrier(0);  // every load is issued before the first MFMA ...
+            mfma_stage();
+            __builtin_amdgcn_sched_barrier(0);  // ... and nothing that consumes one moves up among them
             // one buffer: every wave's fragment reads are done before the next stage overwrites it
             __syncthreads();
-            if (kt + 1 < nk) {
-                store_stage(0);
-                __syncthreads();
-            }
-            continue;
-        } else {
+            store_stage(0, std::true_type{});
+            __syncthreads();
+        }
+        if (nk > 0) mfma_stage();
+        __syncthreads();
+    } else {
+    for (int kt = 0; kt < nk; ++kt) {
+        const int buf = kt & 1;
+        if (kt + 1 < nk) load_stage((kt + 1) * BK);
+        {
 #pragma unroll
         for (int kg = 0; kg < BK / 8; ++kg) {
             float4 af[TM], bf[TN];
@@ -513,8 +558,9 @@ __global__ __launch_bounds__(256, X6 ? 2 : 1) void gemm_rows_vec(RowsArgs g) {
                 }
         }
         }
-        if (kt + 1 < nk) store_stage(buf ^ 1);
+        if (kt + 1 < nk) store_stage(buf ^ 1, std::true_type{});
         __syncthreads();
+    }
     }
 
     ROWS_STAMP(g, 2);
