@@ -166,6 +166,8 @@ int unet_dwconv3x3_bwd_data_bnstats_dwf(const unet_view* x, int n, int h, int w,
  * scratch (overwritten).  The reduction of unet_dwconv3x3_bwd_data_bnstats_dwf's slabs.        */
 int unet_reduce_slabs(float* slabs, int S, int64_t len, float* out, unet_stream_t stream);
 
+/* Workspace bytes of unet_dwconv3x3_bwd_filter; the value covers every view of c channels
+ * (c = c0 + c1 for a concat view, however the channels are split).                             */
 size_t unet_dwconv3x3_bwd_filter_workspace(int n, int h, int w, int c);
 /* d_dw_kernel (3,3,C,1) = sum over pixels of x(shifted) * dy (overwrites). */
 int unet_dwconv3x3_bwd_filter(const unet_view* x, int n, int h, int w,

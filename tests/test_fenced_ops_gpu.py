@@ -100,6 +100,27 @@ def test_reduce_slabs_tails(ops, S, L, skew):
     assert rel_err(host(out), slabs.sum(0)) < 1e-6
 
 
+@pytest.mark.parametrize("n,h,w,c0,c1", [(1, 8, 512, 6, 2), (1, 3, 43, 34, 34)])
+def test_dwconv_bwd_filter_concat_split_off_the_quads(ops, n, h, w, c0, c1):
+    """unet_dwconv3x3_bwd_filter on a concat view with c0 % 4 != 0 and (c0 + c1) % 4 == 0: the scalar flat
+    kernel under a workspace sized by the view-less query for c0 + c1 channels (here exactly that size, every
+    byte 0xFF: NaN).  Its slabs stay inside it (6 + 2: the query sizes 4 slabs where the launch once wrote 16)
+    and every channel is summed (34 + 34: two channel tiles of 64, not one of 17 quads), within
+    test_dwconv_bwd's 1e-5 of float64."""
+    rng = np.random.default_rng(n * h * w + c0)
+    C = c0 + c1
+    up, skip = f32(rng.standard_normal((n, h, w, c0))), f32(rng.standard_normal((n, h, w, c1)))
+    sc, sh = bn_affine(rng, c1)
+    dy = f32(rng.standard_normal((n, h, w, C)))
+    v = ops.View.concat(dev(up), dev(skip), dev(sc), dev(sh))
+    g = mem.empty((3, 3, C, 1))
+    ops.dwconv3x3_bwd_filter(v, n, h, w, dev(dy), g)
+    assert ops.WORKSPACE.sizes == [ops.L.query("unet_dwconv3x3_bwd_filter_workspace", n, h, w, C)]
+    xv = view_value(3, up, None, None, skip, sc, sh, 0.0, 0)
+    _, ddk = K.depthwise3x3_bwd(xv, np.zeros((3, 3, C, 1)), dy)
+    assert rel_err(host(g), ddk) < 1e-5
+
+
 @pytest.mark.parametrize("use_bn", [True, False])
 @pytest.mark.parametrize("c", [4, 48, 68])
 @pytest.mark.parametrize("m,S", [(1, 1), (127, 2), (129, 65)])  # 65 slabs: chunk rows + arrival counters

@@ -88,6 +88,9 @@ VIEW_CASES = [
     (2, 1, 1, 127, 8, 0, 0.0),
     (3, 1, 3, 43, 8, 4, 0.2),
     (0, 1, 3, 43, 68, 0, 0.0),
+    # concat split off the channel quads (c0 % 4 != 0, c0 + c1 a multiple of 4): scalar lanes
+    (3, 1, 3, 43, 34, 34, 0.0),
+    (3, 1, 8, 128, 6, 2, 0.2),
 ]
 
 

@@ -3,7 +3,7 @@
 // stride 1, 'same' zero padding, depth_multiplier 1, kernel (3,3,C,1)).
 //
 // HBM-bound (18 flop per output element): each lane owns one (pixel, 4-channel)
-// quad; consecutive lanes walk consecutive channel quads of one pixel, so every
+// quad (one channel where a source of the view is not a whole number of quads); consecutive lanes walk consecutive channel quads of one pixel, so every
 // wave reads/writes contiguous NHWC rows (coalesced 16-B accesses).  The 3x3 halo
 // re-reads hit L1/L2.  The input is read through an activation view (BN+ReLU,
 // max-pool, concat, dropout fused on load).
@@ -13,7 +13,7 @@ namespace unet {
 
 namespace {
 
-constexpr int kThreads = 256;
+using dw::kThreads;
 
 // 32-bit index math (the launchers check that every tensor has < 2^31 elements)
 __device__ __forceinline__ void decompose(int p, int H, int W, int& n, int& h, int& w) {
@@ -23,20 +23,42 @@ __device__ __forceinline__ void decompose(int p, int H, int W, int& n, int& h, i
     n = t / H;
 }
 
-template <int MODE, bool DROP>
-__device__ __forceinline__ float4 tap4(const DView& v, int n, int hh, int ww, int H, int W, int c) {
-    float4 x = view_load4<MODE>(v, n, hh, ww, H, W, c);
-    if constexpr (DROP) {
-        const uint64_t i = ((uint64_t)((int64_t)(n * H + hh) * W + ww)) * v.C + c;
-        x = mul4(x, drop_mult4(v.seed, i, v.rate, v.inv_keep));
-    }
-    return x;
+// One body per flat kernel over a lane: a channel quad (float4, VEC) or one channel (float).  The lane of channel
+// index cq covers channels [cq * LW, cq * LW + LW).
+template <bool VEC>
+using lane_t = std::conditional_t<VEC, float4, float>;
+template <bool VEC>
+constexpr int LW = VEC ? 4 : 1;
+template <bool VEC>
+__device__ __forceinline__ lane_t<VEC> lane_ld(const float* p) {
+    if constexpr (VEC) return ld4(p);
+    else return *p;
 }
-template <int MODE, bool DROP>
-__device__ __forceinline__ float tap1(const DView& v, int n, int hh, int ww, int H, int W, int c) {
-    float x = view_load1<MODE>(v, n, hh, ww, H, W, c);
-    if constexpr (DROP)
-        x *= drop_mult(v.seed, ((uint64_t)((int64_t)(n * H + hh) * W + ww)) * v.C + c, v.rate, v.inv_keep);
+template <bool VEC>
+__device__ __forceinline__ lane_t<VEC> lane_zero() {
+    if constexpr (VEC) return f4(0.f);
+    else return 0.f;
+}
+__device__ __forceinline__ void lane_st(float* p, float4 x) { st4(p, x); }
+__device__ __forceinline__ void lane_st(float* p, float x) { *p = x; }
+__device__ __forceinline__ float4 lane_fma(float4 a, float4 b, float4 c) { return fma4(a, b, c); }
+__device__ __forceinline__ float lane_fma(float a, float b, float c) { return fmaf(a, b, c); }
+__device__ __forceinline__ float4 lane_add(float4 a, float4 b) { return add4(a, b); }
+__device__ __forceinline__ float lane_add(float a, float b) { return a + b; }
+// dropout of the lane at logical linear index i
+__device__ __forceinline__ float4 lane_drop(const DView& v, uint64_t i, float4 x) {
+    return mul4(x, drop_mult4(v.seed, i, v.rate, v.inv_keep));
+}
+__device__ __forceinline__ float lane_drop(const DView& v, uint64_t i, float x) {
+    return x * drop_mult(v.seed, i, v.rate, v.inv_keep);
+}
+// the view's value at (n, hh, ww), channels c.., dropout applied
+template <int MODE, bool DROP, bool VEC>
+__device__ __forceinline__ lane_t<VEC> tap(const DView& v, int n, int hh, int ww, int H, int W, int c) {
+    lane_t<VEC> x;
+    if constexpr (VEC) x = view_load4<MODE>(v, n, hh, ww, H, W, c);
+    else x = view_load1<MODE>(v, n, hh, ww, H, W, c);
+    if constexpr (DROP) x = lane_drop(v, ((uint64_t)((int64_t)(n * H + hh) * W + ww)) * v.C + c, x);
     return x;
 }
 
@@ -53,37 +75,20 @@ __global__ __launch_bounds__(kThreads) void dw_fwd_kernel(DView v, int N, int H,
         const int p = idx / CQ;
         int n, h, w;
         decompose(p, H, W, n, h, w);
-        if constexpr (VEC) {
-            const int c = cq * 4;
-            float4 acc = f4(0.f);
+        const int c = cq * LW<VEC>;
+        lane_t<VEC> acc = lane_zero<VEC>();
 #pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const int hh = h + i - 1;
-                if (hh < 0 || hh >= H) continue;
+        for (int i = 0; i < 3; ++i) {
+            const int hh = h + i - 1;
+            if (hh < 0 || hh >= H) continue;
 #pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    const int ww = w + j - 1;
-                    if (ww < 0 || ww >= W) continue;
-                    acc = fma4(tap4<MODE, DROP>(v, n, hh, ww, H, W, c), ld4(K + (i * 3 + j) * C + c), acc);
-                }
+            for (int j = 0; j < 3; ++j) {
+                const int ww = w + j - 1;
+                if (ww < 0 || ww >= W) continue;
+                acc = lane_fma(tap<MODE, DROP, VEC>(v, n, hh, ww, H, W, c), lane_ld<VEC>(K + (i * 3 + j) * C + c), acc);
             }
-            st4(Y + p * C + c, acc);
-        } else {
-            const int c = cq;
-            float acc = 0.f;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const int hh = h + i - 1;
-                if (hh < 0 || hh >= H) continue;
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    const int ww = w + j - 1;
-                    if (ww < 0 || ww >= W) continue;
-                    acc = fmaf(tap1<MODE, DROP>(v, n, hh, ww, H, W, c), K[(i * 3 + j) * C + c], acc);
-                }
-            }
-            Y[p * C + c] = acc;
         }
+        lane_st(Y + p * C + c, acc);
     }
 }
 
@@ -103,36 +108,33 @@ __global__ __launch_bounds__(kThreads) void dw_bwd_data_kernel(DView v, int N, i
         const int p = idx / CQ;
         int n, h, w;
         decompose(p, H, W, n, h, w);
-        if constexpr (VEC) {
-            const int c = cq * 4;
-            float4 acc = f4(0.f);
+        const int c = cq * LW<VEC>;
+        lane_t<VEC> acc = lane_zero<VEC>();
 #pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const int hh = h - i + 1;
-                if (hh < 0 || hh >= H) continue;
+        for (int i = 0; i < 3; ++i) {
+            const int hh = h - i + 1;
+            if (hh < 0 || hh >= H) continue;
 #pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    const int ww = w - j + 1;
-                    if (ww < 0 || ww >= W) continue;
-                    acc = fma4(ld4(dY + ((int64_t)(n * H + hh) * W + ww) * C + c), ld4(K + (i * 3 + j) * C + c),
-                               acc);
-                }
+            for (int j = 0; j < 3; ++j) {
+                const int ww = w - j + 1;
+                if (ww < 0 || ww >= W) continue;
+                acc = lane_fma(lane_ld<VEC>(dY + ((int64_t)(n * H + hh) * W + ww) * C + c),
+                               lane_ld<VEC>(K + (i * 3 + j) * C + c), acc);
             }
-            if constexpr (DROP) {
-                const uint64_t li = (uint64_t)p * C + c;
-                acc = mul4(acc, drop_mult4(v.seed, li, v.rate, v.inv_keep));
-            }
-            if constexpr (MODE == UNET_VIEW_PLAIN || MODE == UNET_VIEW_BNRELU) {
-                st4(dx0 + p * C + c, acc);
-            } else if constexpr (MODE == UNET_VIEW_CONCAT) {
-                if (c < v.c0)
-                    st4(dx0 + p * v.c0 + c, acc);
-                else
-                    st4(dx1 + p * v.c1 + (c - v.c0), acc);
-            } else {  // POOL_BNRELU: route to the first max of the 2x2 window (row-major scan)
-                const int W2 = 2 * W;
-                const int64_t b = ((int64_t)(n * 2 * H + 2 * h) * W2 + 2 * w) * v.c0 + c;
-                const int64_t off[4] = {0, v.c0, (int64_t)W2 * v.c0, (int64_t)W2 * v.c0 + v.c0};
+        }
+        if constexpr (DROP) acc = lane_drop(v, (uint64_t)p * C + c, acc);
+        if constexpr (MODE == UNET_VIEW_PLAIN || MODE == UNET_VIEW_BNRELU) {
+            lane_st(dx0 + p * C + c, acc);
+        } else if constexpr (MODE == UNET_VIEW_CONCAT) {
+            if (c < v.c0)
+                lane_st(dx0 + p * v.c0 + c, acc);
+            else
+                lane_st(dx1 + p * v.c1 + (c - v.c0), acc);
+        } else {  // POOL_BNRELU: route to the first max of the 2x2 window (row-major scan)
+            const int W2 = 2 * W;
+            const int64_t b = ((int64_t)(n * 2 * H + 2 * h) * W2 + 2 * w) * v.c0 + c;
+            const int64_t off[4] = {0, v.c0, (int64_t)W2 * v.c0, (int64_t)W2 * v.c0 + v.c0};
+            if constexpr (VEC) {
                 const float4 sc = ld4(v.sc0 + c), sh = ld4(v.sh0 + c);
                 float4 xv[4], g[4];
 #pragma unroll
@@ -140,61 +142,13 @@ __global__ __launch_bounds__(kThreads) void dw_bwd_data_kernel(DView v, int N, i
                     xv[q] = bnrelu4(ld4(v.src0 + b + off[q]), sc, sh);
                     g[q] = ld4(dx0 + b + off[q]);
                 }
-                float best;
-                int arg;
-#define UNET_POOL_ROUTE(comp)                                        \
-    best = xv[0].comp;                                               \
-    arg = 0;                                                         \
-    if (xv[1].comp > best) { best = xv[1].comp; arg = 1; }           \
-    if (xv[2].comp > best) { best = xv[2].comp; arg = 2; }           \
-    if (xv[3].comp > best) { best = xv[3].comp; arg = 3; }           \
-    g[0].comp += arg == 0 ? acc.comp : 0.f;                          \
-    g[1].comp += arg == 1 ? acc.comp : 0.f;                          \
-    g[2].comp += arg == 2 ? acc.comp : 0.f;                          \
-    g[3].comp += arg == 3 ? acc.comp : 0.f;
-                UNET_POOL_ROUTE(x)
-                UNET_POOL_ROUTE(y)
-                UNET_POOL_ROUTE(z)
-                UNET_POOL_ROUTE(w)
-#undef UNET_POOL_ROUTE
+                pool_route(g, xv, acc);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) st4(dx0 + b + off[q], g[q]);
-            }
-        } else {
-            const int c = cq;
-            float acc = 0.f;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const int hh = h - i + 1;
-                if (hh < 0 || hh >= H) continue;
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    const int ww = w - j + 1;
-                    if (ww < 0 || ww >= W) continue;
-                    acc = fmaf(dY[((int64_t)(n * H + hh) * W + ww) * C + c], K[(i * 3 + j) * C + c], acc);
-                }
-            }
-            if constexpr (DROP) acc *= drop_mult(v.seed, (uint64_t)p * C + c, v.rate, v.inv_keep);
-            if constexpr (MODE == UNET_VIEW_PLAIN || MODE == UNET_VIEW_BNRELU) {
-                dx0[p * C + c] = acc;
-            } else if constexpr (MODE == UNET_VIEW_CONCAT) {
-                if (c < v.c0)
-                    dx0[p * v.c0 + c] = acc;
-                else
-                    dx1[p * v.c1 + (c - v.c0)] = acc;
-            } else {
-                const int W2 = 2 * W;
-                const int64_t b = ((int64_t)(n * 2 * H + 2 * h) * W2 + 2 * w) * v.c0 + c;
-                const int64_t off[4] = {0, v.c0, (int64_t)W2 * v.c0, (int64_t)W2 * v.c0 + v.c0};
+            } else {  // one channel: only the maximum's gradient is touched
                 const float sc = v.sc0[c], sh = v.sh0[c];
-                float best = bnrelu(v.src0[b], sc, sh);
-                int arg = 0;
-#pragma unroll
-                for (int q = 1; q < 4; ++q) {
-                    float xq = bnrelu(v.src0[b + off[q]], sc, sh);
-                    if (xq > best) { best = xq; arg = q; }
-                }
-                dx0[b + off[arg]] += acc;
+                dx0[b + off[pool_first_max(bnrelu(v.src0[b], sc, sh), bnrelu(v.src0[b + off[1]], sc, sh),
+                                           bnrelu(v.src0[b + off[2]], sc, sh), bnrelu(v.src0[b + off[3]], sc, sh))]] += acc;
             }
         }
     }
@@ -202,59 +156,42 @@ __global__ __launch_bounds__(kThreads) void dw_bwd_data_kernel(DView v, int N, i
 
 // ---------------------------------------------------------- backward filter ----
 // dk[i,j,c] = sum_p x(p + (i-1, j-1))[c] * dy[p][c].  Block = CT channel lanes x PL
-// pixel lanes over a pixel chunk; fixed-order LDS reduction -> partial[chunk][9][C].
+// pixel lanes over a pixel chunk (CQ lanes per pixel; all three from dw_filter_plan, which derives the grid
+// from the same numbers); fixed-order LDS reduction -> partial[chunk][9][C].
 template <int MODE, bool DROP, bool VEC>
 __global__ __launch_bounds__(kThreads) void dw_bwd_filter_kernel(DView v, int N, int H, int W,
                                                                  const float* __restrict__ dY,
-                                                                 float* __restrict__ part, int64_t ppc) {
+                                                                 float* __restrict__ part, int CQ, int CT, int PL,
+                                                                 int64_t ppc) {
     const int C = v.C;
-    const int CQ = VEC ? C / 4 : C;
-    const int CT = CQ < 64 ? CQ : 64;
-    const int PL = kThreads / CT;
     const int tid = threadIdx.x;
     const int cl = tid % CT;
     const int pl = tid / CT;
     const int cq = blockIdx.x * CT + cl;
+    const int c = cq * LW<VEC>;
     const int P = N * H * W;
     const int p0 = blockIdx.y * (int)ppc;
     const int p1 = p0 + (int)ppc < P ? p0 + (int)ppc : P;
-    __shared__ float4 red[kThreads];
+    __shared__ lane_t<VEC> red[kThreads];
 
     const bool active = pl < PL && cq < CQ;
-    float4 acc[9];
+    lane_t<VEC> acc[9];
 #pragma unroll
-    for (int t = 0; t < 9; ++t) acc[t] = f4(0.f);
+    for (int t = 0; t < 9; ++t) acc[t] = lane_zero<VEC>();
     if (active) {
         for (int p = p0 + pl; p < p1; p += PL) {
             int n, h, w;
             decompose(p, H, W, n, h, w);
-            if constexpr (VEC) {
-                const int c = cq * 4;
-                const float4 g = ld4(dY + p * C + c);
+            const lane_t<VEC> g = lane_ld<VEC>(dY + p * C + c);
 #pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    const int hh = h + i - 1;
-                    if (hh < 0 || hh >= H) continue;
+            for (int i = 0; i < 3; ++i) {
+                const int hh = h + i - 1;
+                if (hh < 0 || hh >= H) continue;
 #pragma unroll
-                    for (int j = 0; j < 3; ++j) {
-                        const int ww = w + j - 1;
-                        if (ww < 0 || ww >= W) continue;
-                        acc[i * 3 + j] = fma4(tap4<MODE, DROP>(v, n, hh, ww, H, W, c), g, acc[i * 3 + j]);
-                    }
-                }
-            } else {
-                const int c = cq;
-                const float g = dY[p * C + c];
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    const int hh = h + i - 1;
-                    if (hh < 0 || hh >= H) continue;
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) {
-                        const int ww = w + j - 1;
-                        if (ww < 0 || ww >= W) continue;
-                        acc[i * 3 + j].x = fmaf(tap1<MODE, DROP>(v, n, hh, ww, H, W, c), g, acc[i * 3 + j].x);
-                    }
+                for (int j = 0; j < 3; ++j) {
+                    const int ww = w + j - 1;
+                    if (ww < 0 || ww >= W) continue;
+                    acc[i * 3 + j] = lane_fma(tap<MODE, DROP, VEC>(v, n, hh, ww, H, W, c), g, acc[i * 3 + j]);
                 }
             }
         }
@@ -266,12 +203,9 @@ __global__ __launch_bounds__(kThreads) void dw_bwd_filter_kernel(DView v, int N,
         red[tid] = acc[t];
         __syncthreads();
         if (pl == 0 && cq < CQ) {
-            float4 s = red[cl];
-            for (int q = 1; q < PL; ++q) s = add4(s, red[q * CT + cl]);
-            if constexpr (VEC)
-                st4(out + t * C + cq * 4, s);
-            else
-                out[t * C + cq] = s.x;
+            lane_t<VEC> s = red[cl];
+            for (int q = 1; q < PL; ++q) s = lane_add(s, red[q * CT + cl]);
+            lane_st(out + t * C + c, s);
         }
         __syncthreads();
     }
@@ -289,151 +223,109 @@ __global__ __launch_bounds__(kThreads) void view_materialize_kernel(DView v, int
         const int p = idx / CQ;
         int n, h, w;
         decompose(p, H, W, n, h, w);
-        if constexpr (VEC)
-            st4(out + p * C + cq * 4, tap4<MODE, DROP>(v, n, h, w, H, W, cq * 4));
-        else
-            out[p * C + cq] = tap1<MODE, DROP>(v, n, h, w, H, W, cq);
+        lane_st(out + p * C + cq * LW<VEC>, tap<MODE, DROP, VEC>(v, n, h, w, H, W, cq * LW<VEC>));
     }
-}
-
-struct FilterPlan {
-    int ctiles;
-    int64_t chunks, ppc;
-};
-FilterPlan filter_plan(int n, int h, int w, int c) {
-    const bool vec = c % 4 == 0;
-    const int CQ = vec ? c / 4 : c;
-    const int CT = CQ < 64 ? CQ : 64;
-    FilterPlan fp;
-    fp.ctiles = (int)cdiv(CQ, CT);
-    const int64_t P = (int64_t)n * h * w;
-    int64_t want = cdiv(2048, fp.ctiles);
-    int64_t maxc = cdiv(P, 256);  // at least ~256 pixels per chunk
-    fp.chunks = want < maxc ? want : maxc;
-    if (fp.chunks < 1) fp.chunks = 1;
-    fp.ppc = cdiv(P, fp.chunks);
-    fp.chunks = cdiv(P, fp.ppc);
-    return fp;
-}
-
-int grid_for(int64_t work) {
-    int64_t g = cdiv(work, kThreads);
-    if (g > 65536) g = 65536;
-    if (g < 1) g = 1;
-    return (int)g;
 }
 
 }  // namespace
 
-static bool view_vec(const unet_view* x) {
-    if (x->mode == UNET_VIEW_CONCAT) return x->c0 % 4 == 0 && x->c1 % 4 == 0;
-    return x->c0 % 4 == 0;
-}
-
-static int check_dims(const unet_view* x, int n, int h, int w, const char* op) {
-    UNET_CHECK_ARG(n > 0 && h > 0 && w > 0, "%s: bad shape n=%d h=%d w=%d", op, n, h, w);
-    const int64_t C = x->c0 + (x->mode == UNET_VIEW_CONCAT ? x->c1 : 0);
-    const int64_t src = (int64_t)n * h * w * C * (x->mode == UNET_VIEW_POOL_BNRELU ? 4 : 1);
-    UNET_CHECK_ARG(src < (int64_t(1) << 31), "%s: tensor too large for 32-bit indexing", op);
-    return 0;
-}
-
 }  // namespace unet
 
 using namespace unet;
+using dw::DW_TILED;
+
+// The checks every entry point shares, then the plan of the call.  Returns 0 or -1.
+static int plan_for(const unet_view* x, int n, int h, int w, const char* op, dw::DwPlan& p) {
+    if (check_view(x, op)) return -1;
+    UNET_CHECK_ARG(n > 0 && h > 0 && w > 0, "%s: bad shape n=%d h=%d w=%d", op, n, h, w);
+    UNET_CHECK_ARG(dw::index_fits(x->mode, x->c0, x->c1, n, h, w), "%s: tensor too large for 32-bit indexing", op);
+    p = dw::dw_plan(x->mode, x->c0, x->c1, n, h, w);
+    return 0;
+}
 
 extern "C" int unet_dwconv3x3_fwd(const unet_view* x, int n, int h, int w, const float* dw_kernel, float* y,
                                   unet_stream_t stream) {
-    if (check_view(x, "unet_dwconv3x3_fwd") || check_dims(x, n, h, w, "unet_dwconv3x3_fwd")) return -1;
-    UNET_CHECK_ARG(dw_kernel && y, "unet_dwconv3x3_fwd: null kernel/output");
+    const char* op = "unet_dwconv3x3_fwd";
+    dw::DwPlan p;
+    if (plan_for(x, n, h, w, op, p)) return -1;
+    UNET_CHECK_ARG(dw_kernel && y, "%s: null kernel/output", op);
     const DView v = make_dview(*x);
-    const bool vec = view_vec(x);
-    if (vec && dw_tiled_ok(v.C))
-        return dw_tiled_fwd(v, x->mode, x->drop_rate > 0.f, n, h, w, dw_kernel, y, as_stream(stream));
-    const int64_t work = (int64_t)n * h * w * (vec ? v.C / 4 : v.C);
     hipStream_t st = as_stream(stream);
-    const int grid = grid_for(work);
+    if (p.route == DW_TILED) return dw_tiled_fwd(p, v, x->mode, x->drop_rate > 0.f, dw_kernel, y, st);
     with_view(x->mode, x->drop_rate > 0.f, [&](auto M, auto D) {
-        with_bool(vec, [&](auto V) {
-            dw_fwd_kernel<M(), D(), V()><<<grid, kThreads, 0, st>>>(v, n, h, w, dw_kernel, y);
+        with_bool(p.vec(), [&](auto V) {
+            dw_fwd_kernel<M(), D(), V()><<<p.flat_grid, kThreads, 0, st>>>(v, n, h, w, dw_kernel, y);
         });
     });
-    UNET_CHECK_LAUNCH("unet_dwconv3x3_fwd");
+    UNET_CHECK_LAUNCH(op);
     return 0;
 }
 
 extern "C" int unet_view_materialize(const unet_view* x, int n, int h, int w, float* out, unet_stream_t stream) {
-    if (check_view(x, "unet_view_materialize") || check_dims(x, n, h, w, "unet_view_materialize")) return -1;
-    UNET_CHECK_ARG(out, "unet_view_materialize: null output");
+    const char* op = "unet_view_materialize";
+    dw::DwPlan p;
+    if (plan_for(x, n, h, w, op, p)) return -1;
+    UNET_CHECK_ARG(out, "%s: null output", op);
     const DView v = make_dview(*x);
-    const bool vec = view_vec(x);
-    const int64_t work = (int64_t)n * h * w * (vec ? v.C / 4 : v.C);
     hipStream_t st = as_stream(stream);
-    const int grid = grid_for(work);
-    with_view(x->mode, x->drop_rate > 0.f, [&](auto M, auto D) {
-        with_bool(vec, [&](auto V) {
-            view_materialize_kernel<M(), D(), V()><<<grid, kThreads, 0, st>>>(v, n, h, w, out);
+    with_view(x->mode, x->drop_rate > 0.f, [&](auto M, auto D) {  // flat kernels only, whatever the route
+        with_bool(p.vec(), [&](auto V) {
+            view_materialize_kernel<M(), D(), V()><<<p.flat_grid, kThreads, 0, st>>>(v, n, h, w, out);
         });
     });
-    UNET_CHECK_LAUNCH("unet_view_materialize");
+    UNET_CHECK_LAUNCH(op);
     return 0;
 }
 
 extern "C" int unet_dwconv3x3_bwd_data(const unet_view* x, int n, int h, int w, const float* dw_kernel,
                                        const float* dy, float* dx0, float* dx1, unet_stream_t stream) {
-    if (check_view(x, "unet_dwconv3x3_bwd_data") || check_dims(x, n, h, w, "unet_dwconv3x3_bwd_data")) return -1;
-    UNET_CHECK_ARG(dw_kernel && dy && dx0, "unet_dwconv3x3_bwd_data: null pointer");
-    UNET_CHECK_ARG(x->mode != UNET_VIEW_CONCAT || dx1, "unet_dwconv3x3_bwd_data: CONCAT view needs dx1");
+    const char* op = "unet_dwconv3x3_bwd_data";
+    dw::DwPlan p;
+    if (plan_for(x, n, h, w, op, p)) return -1;
+    UNET_CHECK_ARG(dw_kernel && dy && dx0, "%s: null pointer", op);
+    UNET_CHECK_ARG(x->mode != UNET_VIEW_CONCAT || dx1, "%s: CONCAT view needs dx1", op);
     const DView v = make_dview(*x);
-    const bool vec = view_vec(x);
-    if (vec && dw_tiled_ok(v.C))
-        return dw_tiled_bwd_data(v, x->mode, x->drop_rate > 0.f, n, h, w, dw_kernel, dy, dx0, dx1,
-                                 as_stream(stream));
-    const int64_t work = (int64_t)n * h * w * (vec ? v.C / 4 : v.C);
     hipStream_t st = as_stream(stream);
-    const int grid = grid_for(work);
+    if (p.route == DW_TILED) return dw_tiled_bwd_data(p, v, x->mode, x->drop_rate > 0.f, dw_kernel, dy, dx0, dx1, st);
     with_view(x->mode, x->drop_rate > 0.f, [&](auto M, auto D) {
-        with_bool(vec, [&](auto V) {
-            dw_bwd_data_kernel<M(), D(), V()><<<grid, kThreads, 0, st>>>(v, n, h, w, dw_kernel, dy, dx0, dx1);
+        with_bool(p.vec(), [&](auto V) {
+            dw_bwd_data_kernel<M(), D(), V()><<<p.flat_grid, kThreads, 0, st>>>(v, n, h, w, dw_kernel, dy, dx0, dx1);
         });
     });
-    UNET_CHECK_LAUNCH("unet_dwconv3x3_bwd_data");
+    UNET_CHECK_LAUNCH(op);
     return 0;
 }
 
 extern "C" int unet_dwconv3x3_bwd_data_bnstats_slabs(const unet_view* x, int n, int h, int w) {
-    if (!x || (x->mode != UNET_VIEW_POOL_BNRELU && x->mode != UNET_VIEW_BNRELU) || n <= 0 || h <= 0 || w <= 0)
-        return 0;
-    if (!view_vec(x) || !dw_tiled_ok(x->c0)) return 0;
-    return (int)dw_tiled_ntiles(n, h, w, x->c0);
+    return x ? dw::dw_bnstats_slabs(x->mode, x->c0, n, h, w) : 0;
 }
 
 extern "C" int unet_dwconv3x3_bwd_data_bnstats(const unet_view* x, int n, int h, int w, const float* dw_kernel,
                                                const float* dy, float* dx0, const float* mean, const float* rstd,
                                                float* bn_partials, unet_stream_t stream) {
     const char* op = "unet_dwconv3x3_bwd_data_bnstats";
-    if (check_view(x, op) || check_dims(x, n, h, w, op)) return -1;
+    dw::DwPlan p;
+    if (plan_for(x, n, h, w, op, p)) return -1;
     UNET_CHECK_ARG(dw_kernel && dy && dx0 && bn_partials, "%s: null pointer", op);
-    UNET_CHECK_ARG(unet_dwconv3x3_bwd_data_bnstats_slabs(x, n, h, w) > 0,
+    UNET_CHECK_ARG(dw::dw_bnstats_slabs(x->mode, x->c0, n, h, w) > 0,
                    "%s: needs a POOL_BNRELU or BNRELU view with channels %% 4 == 0 (tiled path)", op);
     UNET_CHECK_ARG((mean == nullptr) == (rstd == nullptr), "%s: mean and rstd go together", op);
-    const DView v = make_dview(*x);
-    return dw_tiled_bwd_data_bnstats(v, x->mode, x->drop_rate > 0.f, n, h, w, dw_kernel, dy, dx0, mean, rstd, bn_partials,
-                                     as_stream(stream));
+    return dw_tiled_bwd_data_bnstats(p, make_dview(*x), x->mode, x->drop_rate > 0.f, dw_kernel, dy, dx0, mean, rstd,
+                                     bn_partials, as_stream(stream));
 }
 
 extern "C" int unet_dwconv3x3_bwd_data_bnstats_dwf(const unet_view* x, int n, int h, int w, const float* dw_kernel,
                                                    const float* dy, float* dx0, const float* mean, const float* rstd,
                                                    float* bn_partials, float* dw_partials, unet_stream_t stream) {
     const char* op = "unet_dwconv3x3_bwd_data_bnstats_dwf";
-    if (check_view(x, op) || check_dims(x, n, h, w, op)) return -1;
+    dw::DwPlan p;
+    if (plan_for(x, n, h, w, op, p)) return -1;
     UNET_CHECK_ARG(dw_kernel && dy && dx0 && bn_partials && dw_partials, "%s: null pointer", op);
-    UNET_CHECK_ARG(x->mode == UNET_VIEW_BNRELU && x->drop_rate == 0.f && unet_dwconv3x3_bwd_data_bnstats_slabs(x, n, h, w) > 0,
+    UNET_CHECK_ARG(dw::dw_bnstats_dwf_ok(x->mode, x->c0, x->drop_rate, n, h, w),
                    "%s: needs a BNRELU view without dropout, channels %% 4 == 0 (tiled path)", op);
     UNET_CHECK_ARG((mean == nullptr) == (rstd == nullptr), "%s: mean and rstd go together", op);
     UNET_CHECK_ARG((uintptr_t)dw_partials % 16 == 0, "%s: dw_partials must be 16-B aligned", op);
-    const DView v = make_dview(*x);
-    return dw_tiled_bwd_data_bnstats(v, x->mode, false, n, h, w, dw_kernel, dy, dx0, mean, rstd, bn_partials,
+    return dw_tiled_bwd_data_bnstats(p, make_dview(*x), x->mode, false, dw_kernel, dy, dx0, mean, rstd, bn_partials,
                                      as_stream(stream), dw_partials);
 }
 
@@ -443,39 +335,32 @@ extern "C" int unet_reduce_slabs(float* slabs, int S, int64_t len, float* out, u
 }
 
 extern "C" size_t unet_dwconv3x3_bwd_filter_workspace(int n, int h, int w, int c) {
-    if (n <= 0 || h <= 0 || w <= 0 || c <= 0) return 0;
-    if (dw_tiled_ok(c)) return align_up(dw_tiled_filter_partials(n, h, w, c) * sizeof(float), 256);
-    FilterPlan fp = filter_plan(n, h, w, c);
-    return align_up((size_t)fp.chunks * 9 * c * sizeof(float), 256);
+    return dw::dw_filter_workspace(n, h, w, c);
 }
 
 extern "C" int unet_dwconv3x3_bwd_filter(const unet_view* x, int n, int h, int w, const float* dy,
                                          float* d_dw_kernel, void* ws, size_t ws_bytes, unet_stream_t stream) {
-    if (check_view(x, "unet_dwconv3x3_bwd_filter") || check_dims(x, n, h, w, "unet_dwconv3x3_bwd_filter"))
-        return -1;
-    UNET_CHECK_ARG(dy && d_dw_kernel, "unet_dwconv3x3_bwd_filter: null pointer");
+    const char* op = "unet_dwconv3x3_bwd_filter";
+    dw::DwPlan p;
+    if (plan_for(x, n, h, w, op, p)) return -1;
+    UNET_CHECK_ARG(dy && d_dw_kernel, "%s: null pointer", op);
+    const dw::DwFilterPlan f = dw::dw_filter_plan(x->mode, x->c0, x->c1, n, h, w);
+    // the caller sized ws by the view-less query, which covers every view of these channels
+    const size_t need = dw::dw_filter_workspace(n, h, w, p.C);
+    UNET_CHECK_ARG(ws && ws_bytes >= need, "%s: workspace %zu < %zu", op, ws_bytes, need);
     const DView v = make_dview(*x);
-    const size_t need = unet_dwconv3x3_bwd_filter_workspace(n, h, w, v.C);
-    UNET_CHECK_ARG(ws && ws_bytes >= need, "unet_dwconv3x3_bwd_filter: workspace %zu < %zu", ws_bytes, need);
-    const bool vec = view_vec(x);
-    if (vec && dw_tiled_ok(v.C)) {
-        int S = 0;
-        float* part = static_cast<float*>(ws);
-        int rc = dw_tiled_bwd_filter(v, x->mode, x->drop_rate > 0.f, n, h, w, dy, part, &S, as_stream(stream));
-        if (rc) return rc;
-        return reduce_slabs(part, S, (int64_t)9 * v.C, d_dw_kernel, (int64_t)9 * v.C, (int64_t)9 * v.C,
-                            as_stream(stream));
-    }
-    FilterPlan fp = filter_plan(n, h, w, v.C);
     hipStream_t st = as_stream(stream);
-    dim3 grid(fp.ctiles, (unsigned)fp.chunks);
     float* part = static_cast<float*>(ws);
-    with_view(x->mode, x->drop_rate > 0.f, [&](auto M, auto D) {
-        with_bool(vec, [&](auto V) {
-            dw_bwd_filter_kernel<M(), D(), V()><<<grid, kThreads, 0, st>>>(v, n, h, w, dy, part, fp.ppc);
+    if (p.route == DW_TILED) {
+        if (int rc = dw_tiled_bwd_filter(f, v, x->mode, x->drop_rate > 0.f, dy, part, st)) return rc;
+    } else {
+        with_view(x->mode, x->drop_rate > 0.f, [&](auto M, auto D) {
+            with_bool(p.vec(), [&](auto V) {
+                dw_bwd_filter_kernel<M(), D(), V()><<<dim3(f.grid_x, f.grid_y), kThreads, 0, st>>>(
+                    v, n, h, w, dy, part, p.CQ, f.CT, f.PL, f.ppc);
+            });
         });
-    });
-    UNET_CHECK_LAUNCH("unet_dwconv3x3_bwd_filter");
-    return reduce_slabs(part, (int)fp.chunks, (int64_t)9 * v.C, d_dw_kernel, (int64_t)9 * v.C, (int64_t)9 * v.C,
-                        st);
+        UNET_CHECK_LAUNCH(op);
+    }
+    return reduce_slabs(part, f.S, (int64_t)9 * p.C, d_dw_kernel, (int64_t)9 * p.C, (int64_t)9 * p.C, st);
 }

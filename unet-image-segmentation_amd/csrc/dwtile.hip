@@ -16,7 +16,9 @@ namespace unet {
 
 namespace {
 
-constexpr int TH = 8;
+using dw::DwFilterPlan;
+using dw::DwPlan;
+using dw::TH;
 
 template <int QT>
 struct Geom {
@@ -122,6 +124,28 @@ __device__ __forceinline__ void tile_coords(int b, int tiles_w, int tiles_h, int
     n = b / tiles_h;
     h0 = th * TH;
     w0 = tw * TW;
+}
+
+// dst[0..3] = the sum of v over the TW column lanes of this lane's channel quad, in column order, through T
+template <int QT>
+__device__ __forceinline__ void column_sum_store(float4* T, float4 v, int q, int col, float* dst) {
+    __syncthreads();
+    T[threadIdx.x] = v;
+    __syncthreads();
+    if (col == 0) {
+        float4 s = T[q];
+        for (int cl = 1; cl < Geom<QT>::TW; ++cl) s = add4(s, T[cl * QT + q]);
+        st4(dst, s);
+    }
+}
+
+// BatchNorm-backward partial sums of one element: g masked by the ReLU (x = z sc + sh > 0), and that times
+// xhat = (z - mu) rs
+__device__ __forceinline__ void stats_add(float4& s1, float4& s2, float4 x, float4 g, float4 z, float4 smu, float4 srs) {
+    const float4 gm = make_float4(x.x > 0.f ? g.x : 0.f, x.y > 0.f ? g.y : 0.f, x.z > 0.f ? g.z : 0.f, x.w > 0.f ? g.w : 0.f);
+    s1 = add4(s1, gm);
+    const float4 xh = make_float4((z.x - smu.x) * srs.x, (z.y - smu.y) * srs.y, (z.z - smu.z) * srs.z, (z.w - smu.w) * srs.w);
+    s2 = fma4(gm, xh, s2);
 }
 
 template <int MODE, bool DROP, int QT>
@@ -262,15 +286,7 @@ __global__ __launch_bounds__(256, DWF ? 2 : 3) void dw_tile_bwd_data(DView v, in
             st4(dx0 + (int64_t)p * C + c, acc);
             if constexpr (STATS && MODE == UNET_VIEW_BNRELU) {  // dx0 is the whole da of the view's block
                 const float4 zr = DWF ? zq : ld4(v.src0 + (int64_t)p * C + c);
-                const float4 sc = ld4(v.sc0 + c), sh = ld4(v.sh0 + c);
-                const float4 gm = make_float4(fmaf(zr.x, sc.x, sh.x) > 0.f ? acc.x : 0.f,
-                                              fmaf(zr.y, sc.y, sh.y) > 0.f ? acc.y : 0.f,
-                                              fmaf(zr.z, sc.z, sh.z) > 0.f ? acc.z : 0.f,
-                                              fmaf(zr.w, sc.w, sh.w) > 0.f ? acc.w : 0.f);
-                s1 = add4(s1, gm);
-                const float4 xh = make_float4((zr.x - smu.x) * srs.x, (zr.y - smu.y) * srs.y,
-                                              (zr.z - smu.z) * srs.z, (zr.w - smu.w) * srs.w);
-                s2 = fma4(gm, xh, s2);
+                stats_add(s1, s2, fma4(zr, ld4(v.sc0 + c), ld4(v.sh0 + c)), acc, zr, smu, srs);
             }
         } else if constexpr (MODE == UNET_VIEW_CONCAT) {
             if (c < v.c0)
@@ -289,35 +305,12 @@ __global__ __launch_bounds__(256, DWF ? 2 : 3) void dw_tile_bwd_data(DView v, in
                 xv[qq] = bnrelu4(zr[qq], sc, sh);
                 g[qq] = ld4(dx0 + b + off[qq]);
             }
-#define UNET_ROUTE(comp)                                                   \
-    {                                                                      \
-        float best = xv[0].comp;                                           \
-        int arg = 0;                                                       \
-        if (xv[1].comp > best) { best = xv[1].comp; arg = 1; }             \
-        if (xv[2].comp > best) { best = xv[2].comp; arg = 2; }             \
-        if (xv[3].comp > best) { best = xv[3].comp; arg = 3; }             \
-        g[0].comp += arg == 0 ? acc.comp : 0.f;                            \
-        g[1].comp += arg == 1 ? acc.comp : 0.f;                            \
-        g[2].comp += arg == 2 ? acc.comp : 0.f;                            \
-        g[3].comp += arg == 3 ? acc.comp : 0.f;                            \
-    }
-            UNET_ROUTE(x)
-            UNET_ROUTE(y)
-            UNET_ROUTE(z)
-            UNET_ROUTE(w)
-#undef UNET_ROUTE
+            pool_route(g, xv, acc);
 #pragma unroll
             for (int qq = 0; qq < 4; ++qq) st4(dx0 + b + off[qq], g[qq]);
             if constexpr (STATS) {
 #pragma unroll
-                for (int qq = 0; qq < 4; ++qq) {
-                    const float4 gm = make_float4(xv[qq].x > 0.f ? g[qq].x : 0.f, xv[qq].y > 0.f ? g[qq].y : 0.f,
-                                                  xv[qq].z > 0.f ? g[qq].z : 0.f, xv[qq].w > 0.f ? g[qq].w : 0.f);
-                    s1 = add4(s1, gm);
-                    const float4 xh = make_float4((zr[qq].x - smu.x) * srs.x, (zr[qq].y - smu.y) * srs.y,
-                                                  (zr[qq].z - smu.z) * srs.z, (zr[qq].w - smu.w) * srs.w);
-                    s2 = fma4(gm, xh, s2);
-                }
+                for (int qq = 0; qq < 4; ++qq) stats_add(s1, s2, xv[qq], g[qq], zr[qq], smu, srs);
             }
         }
     }
@@ -346,24 +339,10 @@ __global__ __launch_bounds__(256, DWF ? 2 : 3) void dw_tile_bwd_data(DView v, in
             st4(out + t * C + cbase + 4 * qq, s);
         }
     }
-    if constexpr (STATS) {  // fixed-order reduction over the TW column lanes of each channel quad
+    if constexpr (STATS) {
         float* out = bnpart + (int64_t)tile * 2 * C;
-        __syncthreads();
-        T[threadIdx.x] = s1;
-        __syncthreads();
-        if (col == 0) {
-            float4 t = T[q];
-            for (int cl = 1; cl < G::TW; ++cl) t = add4(t, T[cl * QT + q]);
-            st4(out + c, t);
-        }
-        __syncthreads();
-        T[threadIdx.x] = s2;
-        __syncthreads();
-        if (col == 0) {
-            float4 t = T[q];
-            for (int cl = 1; cl < G::TW; ++cl) t = add4(t, T[cl * QT + q]);
-            st4(out + C + c, t);
-        }
+        column_sum_store<QT>(T, s1, q, col, out + c);
+        column_sum_store<QT>(T, s2, q, col, out + C + c);
     }
 }
 
@@ -423,7 +402,8 @@ __global__ __launch_bounds__(256, 2) void dw_tile_bwd_filter(DView v, int N, int
             }
         }
     }
-    // fixed-order reduction over the TW column lanes of each channel quad
+    // fixed-order reduction over the TW column lanes of each channel quad (column_sum_store, written out: the
+    // call compiled to slower code here)
     float* out = part + (int64_t)blockIdx.x * 9 * C;
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
@@ -438,77 +418,38 @@ __global__ __launch_bounds__(256, 2) void dw_tile_bwd_filter(DView v, int N, int
     }
 }
 
-int qt_for(int C) {
-    if (C % 4) return 0;
-    if (C % 64 == 0) return 16;  // (8 quads x 32 columns measured -0.6 % img/s, round 2)
-    const int q = C / 4;
-    return (q == 1 || q == 2 || q == 4 || q == 8) ? q : 0;
-}
-
-struct TilePlan {
-    int qt, tw, tiles_w, tiles_h, chunks, ntiles, n;
-};
-TilePlan tile_plan(int N, int H, int W, int C) {
-    TilePlan p;
-    p.qt = qt_for(C);
-    p.tw = p.qt ? 256 / p.qt : 1;
-    p.tiles_w = (int)cdiv(W, p.tw);
-    p.tiles_h = (int)cdiv(H, TH);
-    p.chunks = p.qt ? C / (4 * p.qt) : 1;
-    p.ntiles = N * p.tiles_w * p.tiles_h;
-    p.n = N;
-    return p;
-}
-int filter_blocks(const TilePlan& p) {
-    // persistent blocks over all channel chunks: 1024 (~4 per CU), 512 at batch <= 8 (fewer slabs to
-    // reduce; configs[4] batch 8 -0.8 %, configs[3] and batch 16 / 32 within the spread or slower with
-    // 512, profiles/r5d_step_ab.txt d8_* / d16_* / dq_*)
-    int target = lab_knob("UNET_DWF_BLOCKS", p.n <= lab_knob("UNET_DWF_SMALL_N", 8) ? 512 : 1024);
-    if (target < 1) target = 1024;
-    int g = (int)cdiv(target, p.chunks);
-    if (g > p.ntiles) g = p.ntiles;
-    if (g < 1) g = 1;
-    return g;
-}
-
 }  // namespace
 
-bool dw_tiled_ok(int C) { return qt_for(C) != 0; }
-
-int dw_tiled_fwd(const DView& v, int mode, bool drop, int N, int H, int W, const float* K, float* Y, hipStream_t st) {
-    TilePlan p = tile_plan(N, H, W, v.C);
+int dw_tiled_fwd(const DwPlan& p, const DView& v, int mode, bool drop, const float* K, float* Y, hipStream_t st) {
     dim3 grid((unsigned)p.ntiles, (unsigned)p.chunks);
     with_view(mode, drop, [&](auto M, auto D) {
         with_int<16, 8, 4, 2, 1>(p.qt, [&](auto Q) {
-            dw_tile_fwd<M(), D(), Q()><<<grid, 256, 0, st>>>(v, N, H, W, p.tiles_w, p.tiles_h, K, Y);
+            dw_tile_fwd<M(), D(), Q()><<<grid, 256, 0, st>>>(v, p.n, p.h, p.w, p.tiles_w, p.tiles_h, K, Y);
         });
     });
     UNET_CHECK_LAUNCH("dwconv3x3_fwd(tiled)");
     return 0;
 }
 
-int dw_tiled_bwd_data(const DView& v, int mode, bool drop, int N, int H, int W, const float* K, const float* dY,
-                      float* dx0, float* dx1, hipStream_t st) {
-    TilePlan p = tile_plan(N, H, W, v.C);
+int dw_tiled_bwd_data(const DwPlan& p, const DView& v, int mode, bool drop, const float* K, const float* dY, float* dx0,
+                      float* dx1, hipStream_t st) {
     dim3 grid((unsigned)p.ntiles, (unsigned)p.chunks);
     with_view(mode, drop, [&](auto M, auto D) {
         with_int<16, 8, 4, 2, 1>(p.qt, [&](auto Q) {
-            dw_tile_bwd_data<M(), D(), Q()><<<grid, 256, 0, st>>>(v, N, H, W, p.tiles_w, p.tiles_h, K, dY, dx0, dx1);
+            dw_tile_bwd_data<M(), D(), Q()><<<grid, 256, 0, st>>>(v, p.n, p.h, p.w, p.tiles_w, p.tiles_h, K, dY, dx0, dx1);
         });
     });
     UNET_CHECK_LAUNCH("dwconv3x3_bwd_data(tiled)");
     return 0;
 }
 
-int dw_tiled_bwd_data_bnstats(const DView& v, int mode, bool drop, int N, int H, int W, const float* K,
-                              const float* dY, float* dx0, const float* mu, const float* rs, float* bnpart,
-                              hipStream_t st, float* dwpart) {
-    TilePlan p = tile_plan(N, H, W, v.C);
+int dw_tiled_bwd_data_bnstats(const DwPlan& p, const DView& v, int mode, bool drop, const float* K, const float* dY,
+                              float* dx0, const float* mu, const float* rs, float* bnpart, hipStream_t st, float* dwpart) {
     dim3 grid((unsigned)p.ntiles, (unsigned)p.chunks);
     if (dwpart) {  // (BNRELU view, no dropout: checked by the caller)
         with_int<16, 8, 4, 2, 1>(p.qt, [&](auto Q) {
             dw_tile_bwd_data<UNET_VIEW_BNRELU, false, Q(), true, true><<<grid, 256, 0, st>>>(
-                v, N, H, W, p.tiles_w, p.tiles_h, K, dY, dx0, nullptr, mu, rs, bnpart, dwpart);
+                v, p.n, p.h, p.w, p.tiles_w, p.tiles_h, K, dY, dx0, nullptr, mu, rs, bnpart, dwpart);
         });
         UNET_CHECK_LAUNCH("dwconv3x3_bwd_data_bnstats(tiled, filter gradient)");
         return 0;
@@ -516,7 +457,7 @@ int dw_tiled_bwd_data_bnstats(const DView& v, int mode, bool drop, int N, int H,
     with_int<UNET_VIEW_POOL_BNRELU, UNET_VIEW_BNRELU>(mode, [&](auto M) {
         with_bool(drop, [&](auto D) {
             with_int<16, 8, 4, 2, 1>(p.qt, [&](auto Q) {
-                dw_tile_bwd_data<M(), D(), Q(), true><<<grid, 256, 0, st>>>(v, N, H, W, p.tiles_w, p.tiles_h, K, dY,
+                dw_tile_bwd_data<M(), D(), Q(), true><<<grid, 256, 0, st>>>(v, p.n, p.h, p.w, p.tiles_w, p.tiles_h, K, dY,
                                                                             dx0, nullptr, mu, rs, bnpart);
             });
         });
@@ -525,27 +466,18 @@ int dw_tiled_bwd_data_bnstats(const DView& v, int mode, bool drop, int N, int H,
     return 0;
 }
 
-size_t dw_tiled_ntiles(int N, int H, int W, int C) { return (size_t)tile_plan(N, H, W, C).ntiles; }
-
-size_t dw_tiled_filter_partials(int N, int H, int W, int C) {
-    TilePlan p = tile_plan(N, H, W, C);
-    return (size_t)filter_blocks(p) * 9 * C;
-}
-
-int dw_tiled_bwd_filter(const DView& v, int mode, bool drop, int N, int H, int W, const float* dY, float* part,
-                        int* S_out, hipStream_t st) {
+int dw_tiled_bwd_filter(const DwFilterPlan& f, const DView& v, int mode, bool drop, const float* dY, float* part,
+                        hipStream_t st) {
     const unsigned lds_pad = (unsigned)lab_knob("UNET_DWF_LDSPAD", 0);  // lab: dynamic LDS pad (fewer blocks per CU)
-    TilePlan p = tile_plan(N, H, W, v.C);
-    const int G = filter_blocks(p);
-    dim3 grid((unsigned)G, (unsigned)p.chunks);
+    const DwPlan& p = f.p;
+    dim3 grid(f.grid_x, f.grid_y);
     with_view(mode, drop, [&](auto M, auto D) {
         with_int<16, 8, 4, 2, 1>(p.qt, [&](auto Q) {
-            dw_tile_bwd_filter<M(), D(), Q()><<<grid, 256, lds_pad, st>>>(v, N, H, W, p.tiles_w, p.tiles_h, p.ntiles,
+            dw_tile_bwd_filter<M(), D(), Q()><<<grid, 256, lds_pad, st>>>(v, p.n, p.h, p.w, p.tiles_w, p.tiles_h, p.ntiles,
                                                                           dY, part);
         });
     });
     UNET_CHECK_LAUNCH("dwconv3x3_bwd_filter(tiled)");
-    *S_out = G;
     return 0;
 }
 
