@@ -292,3 +292,63 @@ def adamw_update(p, g, m, v, step, lr, wd, beta1=0.9, beta2=0.999, eps=1e-7):
     alpha = lr * np.sqrt(1 - beta2 ** step) / (1 - beta1 ** step)
     p = p - (m * alpha) / (np.sqrt(v) + eps)
     return p, m, v
+
+
+def adamw_update_bound(p, g, m, v, lr, wd, beta1, beta2, eps, alpha, grad_scale=1.0):
+    """The device kernel's update (csrc/adamw.hip), operation by operation in float64, with the
+    running float32 rounding-error bound of that operation sequence beside it.
+
+    The constants are taken as the host passes them, each a float32 cast to float64: lr*wd as a
+    float32 product, 1 - float32(beta), eps, alpha (optim.AdamW.alpha(t)) and grad_scale.  With
+    u = 2^-24 every operation adds u*|its result| and earlier errors propagate through the later
+    operations' derivatives; sqrt contributes e_v/(2s) + u*s, the quotient
+    e_num/den + |r|*e_den/den + u*|r|.  u*|result| is the rounding error of a NORMAL float32 only:
+    the square of a gradient below ~1e-19 is subnormal or zero (gradients that small occur in a real
+    step, e.g. without BatchNorm), so every operation also adds 2^-126, the smallest normal number --
+    an absolute error that covers gradual underflow and flush-to-zero of operands and results alike
+    (~1e-38: nothing next to a value that matters).  Where that leaves e_v not small against v the
+    first-order sqrt term is replaced by the exact min(e_v/s, sqrt(e_v)).  A float32 evaluation that
+    rounds after every operation stays within 1 x the bound (tests/test_adamw_bound_host.py); fused
+    multiply-adds only drop roundings.
+    Returns ((p, m, v), (B_p, B_m, B_v)), float64 arrays."""
+    f32 = np.float32
+    u, tiny = 2.0 ** -24, 2.0 ** -126
+    lr_wd = np.float64(f32(lr) * f32(wd))
+    b1c = np.float64(f32(1) - f32(beta1))
+    b2c = np.float64(f32(1) - f32(beta2))
+    eps, alpha, gs = np.float64(f32(eps)), np.float64(f32(alpha)), np.float64(f32(grad_scale))
+    p, g, m, v = (np.asarray(a, np.float64) for a in (p, g, m, v))
+    g1 = g * gs
+    e_g = u * np.abs(g1) + tiny
+    t1 = p * lr_wd
+    e_t1 = u * np.abs(t1) + tiny
+    p1 = p - t1
+    e_p1 = e_t1 + u * np.abs(p1) + tiny
+    d1 = g1 - m
+    e_d1 = e_g + u * np.abs(d1) + tiny
+    t2 = d1 * b1c
+    e_t2 = e_d1 * b1c + u * np.abs(t2) + tiny
+    m1 = m + t2
+    e_m = e_t2 + u * np.abs(m1) + tiny
+    gg = g1 * g1
+    e_gg = 2.0 * np.abs(g1) * e_g + u * gg + tiny
+    d2 = gg - v
+    e_d2 = e_gg + u * np.abs(d2) + tiny
+    t3 = d2 * b2c
+    e_t3 = e_d2 * b2c + u * np.abs(t3) + tiny
+    v1 = v + t3
+    e_v = e_t3 + u * np.abs(v1) + tiny
+    s = np.sqrt(v1)
+    s_ = np.where(s > 0, s, 1.0)
+    # |sqrt(a) - sqrt(b)| <= min(|a - b| / sqrt(a), sqrt|a - b|); to first order |a - b| / (2 sqrt(a))
+    e_s = np.where(e_v <= 1e-3 * v1, e_v / (2.0 * s_), np.minimum(np.where(s > 0, e_v / s_, np.inf), np.sqrt(e_v)))
+    e_s = e_s + u * s + tiny
+    den = s + eps
+    e_den = e_s + u * den + tiny
+    num = m1 * alpha
+    e_num = e_m * alpha + u * np.abs(num) + tiny
+    r = num / den
+    e_r = e_num / den + np.abs(r) * e_den / den + u * np.abs(r) + tiny
+    p2 = p1 - r
+    e_p = e_p1 + e_r + u * np.abs(p2) + tiny
+    return (p2, m1, v1), (e_p, e_m, e_v)

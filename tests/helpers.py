@@ -104,6 +104,128 @@ def step_trace(cid):
     return rec.trace[first:]
 
 
+def engine_state(model):
+    """The whole visible state of a model between steps, cloned: weights, moving statistics, the
+    optimizer's moments (zeros while it has not built them), iteration count, learning rate and
+    hyper-parameters, and the engine's step counter.  Whatever else influences a step is hidden
+    state: buffers, caches, workspaces."""
+    import torch
+    eng, opt = model.engine, model.optimizer
+    zeros = torch.zeros_like(eng.params)
+    return {"params": eng.params.clone(), "stats": eng.stats.clone(),
+            "m": zeros if opt._m is None else opt._m.clone(), "v": zeros.clone() if opt._v is None else opt._v.clone(),
+            "iterations": opt.iterations, "learning_rate": opt.learning_rate, "config": opt.get_config(),
+            "step_count": eng.step_count}
+
+
+def load_engine_state(model, state):
+    eng, opt = model.engine, model.optimizer
+    eng.params.copy_(state["params"])
+    eng.stats.copy_(state["stats"])
+    eng.params_version += 1
+    opt.build(eng.params)
+    opt._m.copy_(state["m"])
+    opt._v.copy_(state["v"])
+    opt.iterations = state["iterations"]
+    opt.learning_rate = state["learning_rate"]
+    eng.step_count = state["step_count"]
+
+
+def set_routes(model, attrs):
+    """TRACE_DEFAULTS plus `attrs` on the model's engine: every routing attribute pinned."""
+    for k, v in {**TRACE_DEFAULTS, **attrs}.items():
+        setattr(model.engine, k, v)
+
+
+def trace_model(cfg, optimizer=None, metrics=None, seed=2301, attrs=None):
+    """A new model of configuration cfg = (input size, classes, BatchNorm, dropout, engine attributes)
+    -- a TRACE_CONFIGS value -- with the routes pinned (attrs replaces the configuration's own) and an
+    AdamW of the given get_config() (default: the traces' 2e-3, 1e-4) compiled in for the dice loss."""
+    from unet_amd.model import UNetModel
+    from unet_amd.optim import AdamW
+    size, ncls, bn, drop, cattrs = cfg
+    model = UNetModel(size, ncls, dropout_rate=drop, use_batch_norm=bn, device="cuda:0", seed=seed)
+    set_routes(model, cattrs if attrs is None else attrs)
+    model.compile(AdamW(**(optimizer or dict(learning_rate=2e-3, weight_decay=1e-4))), "dice_loss", metrics)
+    return model
+
+
+def fresh_model(cfg, state, metrics=None, seed=2301, attrs=None):
+    """trace_model with `state` loaded: a new engine that knows the visible state and nothing else."""
+    model = trace_model(cfg, state["config"], metrics, seed, attrs)
+    load_engine_state(model, state)
+    return model
+
+
+def step_outputs(model, res, n):
+    """Clones of everything a train step of n images leaves behind (after a synchronisation)."""
+    import torch
+    torch.cuda.synchronize()
+    eng, opt = model.engine, model.optimizer
+    return {"result": res.clone(), "prob": eng.acts(n).prob.clone(), "grads": eng.grads.clone(),
+            "params": eng.params.clone(), "stats": eng.stats.clone(), "m": opt._m.clone(), "v": opt._v.clone()}
+
+
+def fresh_step(cfg, state, x, y, metrics=None, seed=2301, attrs=None):
+    """One train step of a fresh model (fresh_model) on (x, y) from `state`, with empty workspaces
+    for the call; returns step_outputs."""
+    from unet_amd import ops
+    model = fresh_model(cfg, state, metrics, seed, attrs)
+    ws, ops.WORKSPACE = ops.WORKSPACE, ops._Workspace()
+    try:
+        res = model.train_step(x, y)
+        return step_outputs(model, res, x.shape[0])
+    finally:
+        ops.WORKSPACE = ws
+
+
+ADAMW_STATES = {"zero": 1, "warm": 7, "cancel": 3, "underflow": 2}  # moment state -> the step t it is taken at
+
+
+def adamw_case(rng, n, state, grad_scale=1.0):
+    """float32 (p, g, m, v) of n elements, as float64: gradients log-uniform over 1e-9..1 with random
+    signs.  "zero": no moments, every 17th gradient zero (0 / (0 + eps) must give 0); "warm": moments
+    of the gradients' scale; "cancel": m = -g/9, which the first-moment update cancels to ~0, and
+    v = 1e-3 g^2 (g as scaled by grad_scale); "underflow": gradients over 1e-44..1e-12, whose squares
+    are subnormal or zero in float32 (a step without BatchNorm has such gradients), m = g/2, and v
+    zero or g^2 in turn."""
+    g = 10.0 ** rng.uniform(-44.0 if state == "underflow" else -9.0, -12.0 if state == "underflow" else 0.0, n)
+    g *= rng.choice([-1.0, 1.0], n)
+    p = rng.standard_normal(n)
+    if state == "underflow":
+        m, v = 0.5 * g, g * g * (np.arange(n) % 2)
+    elif state == "zero":
+        g[::17] = 0.0
+        m, v = np.zeros(n), np.zeros(n)
+    elif state == "warm":
+        m, v = g * rng.uniform(-1.0, 1.0, n), g * g * rng.uniform(0.05, 2.0, n)
+    else:
+        gs = f32(g) * grad_scale
+        m, v = -gs / 9.0, 1e-3 * gs * gs
+    return f32(p), f32(g), f32(m), f32(v)
+
+
+def adamw_f32(p, g, m, v, lr, wd, beta1, beta2, eps, alpha, grad_scale=1.0):
+    """csrc/adamw.hip's adamw1 in float32 NumPy: one rounding after every operation, no contraction."""
+    t = np.float32
+    p, g, m, v = (np.asarray(a, t) for a in (p, g, m, v))
+    lr_wd, b1c, b2c = t(lr) * t(wd), t(1) - t(beta1), t(1) - t(beta2)
+    g = g * t(grad_scale)
+    p = p - p * lr_wd
+    m = m + (g - m) * b1c
+    v = v + (g * g - v) * b2c
+    p = p - (m * t(alpha)) / (np.sqrt(v) + t(eps))
+    return p, m, v
+
+
+def bound_ratio(got, ref, bound):
+    """max |got - ref| / bound (the bound is positive everywhere); inf where `got` is not a number."""
+    d = np.abs(np.asarray(got, np.float64) - ref)
+    if d.size == 0:
+        return 0.0
+    return float(np.where(np.isnan(d), np.inf, d / bound).max())
+
+
 def dev(a):
     import torch
     return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float32))).cuda()

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 import fenced
-from helpers import bn_affine, f32, host, norm_err, rel_err, view_value
+from helpers import ADAMW_STATES, adamw_case, bn_affine, bound_ratio, f32, host, norm_err, rel_err, view_value
 from oracle import keras_ops as K
 
 pytestmark = pytest.mark.gpu
@@ -588,6 +588,70 @@ def test_adamw(ops):
     assert rel_err(host(tp), rp) < 1e-6
     assert rel_err(host(tm), rm) < 1e-6
     assert rel_err(host(tv), rv) < 1e-6
+
+
+ADAMW_GRID = 4096 * 256  # threads of the capped grid: the elements (float4s) of one grid-stride pass
+ADAMW_COUNTS = [4 * ADAMW_GRID + 4 * 300,  # vector kernel, a ragged second grid-stride pass
+                ADAMW_GRID + 257,          # scalar kernel (count % 4 != 0), second pass
+                8, 4,                      # vector kernel, one wave
+                3, 1]                      # scalar kernel
+ADAMW_HYPER = dict(lr=2e-3, wd=1e-4, beta1=0.9, beta2=0.999, eps=1e-7)
+
+
+def _adamw_check(ops, count, state, grad_scale, skew, record_property):
+    """One unet_adamw_step of `count` elements against the float64 restatement of the kernel, element
+    by element: |device - reference| <= 2 x the rounding bound of the kernel's operation sequence (1 x
+    holds for float32 without contraction, test_adamw_bound_host.py; the 2 is the margin for the
+    device's fused multiply-adds).  skew: which of the four buffers starts 4 bytes past a 16-byte
+    boundary.  The autouse fences catch a store past `count`."""
+    from unet_amd.optim import AdamW
+    rng = np.random.default_rng(count % 1000 + 7 * sorted(ADAMW_STATES).index(state))
+    p, g, m, v = adamw_case(rng, count, state, grad_scale)
+    h = ADAMW_HYPER
+    alpha = AdamW(h["lr"], h["wd"], h["beta1"], h["beta2"], h["eps"]).alpha(ADAMW_STATES[state])
+    acc = dict(fence=mem.out_fence)  # updated in place: the wide fences of an output
+    bufs = {"param": mem.inp(p, **acc), "grad": dev(g), "m": mem.inp(m, **acc), "v": mem.inp(v, **acc)}
+    if skew:
+        bufs[skew] = mem.skewed(bufs[skew])
+    ops.adamw_step(bufs["param"], bufs["grad"], bufs["m"], bufs["v"], h["lr"], h["wd"], h["beta1"], h["beta2"],
+                   h["eps"], alpha, grad_scale)
+    ref, bound = K.adamw_update_bound(p, g, m, v, alpha=alpha, grad_scale=grad_scale, **h)
+    assert np.array_equal(host(bufs["grad"]), g)
+    ratios = {nm: bound_ratio(host(bufs[nm]), r, b) for nm, r, b in zip(("param", "m", "v"), ref, bound)}
+    for nm, r in ratios.items():
+        record_property(f"ratio_{nm}", r)
+    print(f"adamw[{count}, {state}, gs {grad_scale}, skew {skew}]: max error / bound = {ratios}")
+    assert all(r <= 2.0 for r in ratios.values()), ratios
+
+
+@pytest.mark.parametrize("grad_scale", [1.0, 0.5])
+@pytest.mark.parametrize("state", sorted(ADAMW_STATES))
+@pytest.mark.parametrize("count", ADAMW_COUNTS)
+def test_adamw_elementwise(ops, count, state, grad_scale, record_property):
+    _adamw_check(ops, count, state, grad_scale, None, record_property)
+
+
+@pytest.mark.parametrize("skew", ["param", "grad", "m", "v"])
+@pytest.mark.parametrize("count,state,grad_scale", [(ADAMW_COUNTS[0], "warm", 0.5), (8, "zero", 1.0),
+                                                    (4, "cancel", 0.5)])
+def test_adamw_skewed_pointer(ops, count, state, grad_scale, skew, record_property):
+    """A count that is a multiple of 4 with ONE buffer off the 16-byte boundary: the float4 kernel
+    is not admissible, the scalar one must give the same values."""
+    _adamw_check(ops, count, state, grad_scale, skew, record_property)
+
+
+def test_adamw_count_zero(ops):
+    """count == 0 returns 0 and touches none of the four buffers."""
+    import ctypes
+    from unet_amd import _lib
+    bufs = [mem.empty(8, output=False) for _ in range(4)]
+    h = ADAMW_HYPER
+    rc = _lib.load().unet_adamw_step(*(ctypes.c_void_p(t.data_ptr()) for t in bufs), 0, h["lr"], h["wd"], h["beta1"],
+                                     h["beta2"], h["eps"], 1e-3, 1.0,
+                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    assert rc == 0
+    assert all(mem.is_untouched(t) for t in bufs)
 
 
 def test_errors_are_loud(ops):
