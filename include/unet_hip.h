@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define UNET_ABI_VERSION 16
+#define UNET_ABI_VERSION 17
 
 typedef void* unet_stream_t; /* hipStream_t */
 
@@ -735,6 +735,27 @@ size_t unet_mask_largest_contour_workspace(int h, int w);
  * launches on `stream`; no kernel waits for another workgroup.                                  */
 int unet_mask_largest_contour(const unsigned char* mask, int h, int w, unet_contour_box* out,
                               void* ws, size_t ws_bytes, unet_stream_t stream);
+
+/* ----- Device-resident training set: batch gather (ABI 17) -----------------------------------
+ * The training input of scripts/train.py (reference :169-220: ImageDataGenerator, rescale 1/255,
+ * horizontal_flip) once the decoded, resized samples live on the device as uint8
+ * (unet_amd/device_data.py): one call builds the fp32 frame batch (c = 3), a second the mask batch
+ * (c = 1, any byte value).
+ *
+ * src: n samples of h * w * c bytes each, dense, at any byte alignment.  slots: b device int32
+ * entries.  An entry e >= 0 takes sample e as stored; e < 0 takes sample ~e mirrored along w (pixel
+ * order reversed, channel order inside a pixel kept).  The decoded index is clamped to [0, n-1] on
+ * the device, the rule the unet_lerp_coord tables follow: no table makes the kernel read outside
+ * src.  dst: (b, h, w, c) fp32,
+ *     dst[i][y][x][k] = (float)src[s][y][flip ? w-1-x : x][k] / 255.0f
+ * with the IEEE divide, correctly rounded: bitwise NumPy's a.astype(float32) / 255.0 (of a[:, ::-1]
+ * where mirrored).  Every element of dst is written and nothing else.
+ * One launch.  w % 4 == 0 with src 4-byte and dst 16-byte aligned takes the 16-byte-store kernel;
+ * any other w or alignment a byte-wise one with the same result.  Refused with an error message and
+ * no launch: a null pointer, n, h, w or b < 1, c outside {1, 3}, h * w * c > 2^31 - 1, dst or slots
+ * not 4-byte aligned.                                                                            */
+int unet_batch_gather_u8(const unsigned char* src, int n, int h, int w, int c, const int* slots,
+                         int b, float* dst, unet_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,8 @@ Same flags and defaults (reference scripts/train.py:71-117): --epochs 30 --batch
 (dataset/train/{train,val}_{frames,masks}/image), same seed (2301), rescale 1/255,
 synchronised horizontal flips for training, same callbacks (ModelCheckpoint on
 val_mean_io_u, EarlyStopping patience 10, ReduceLROnPlateau factor 0.2 patience 3).
-Extras: --synthetic N (no dataset needed), data-parallel via torchrun env (one process per
+Extras: --synthetic N (no dataset needed), --device_loader (the decoded training set stays on the
+GPU as uint8, batches are built there; same batches), data-parallel via torchrun env (one process per
 GPU, each rank takes its shard of every global batch).  The model file is the engine's
 neutral .npz weight file (Keras names and layouts), whatever the extension.
 """
@@ -58,6 +59,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     parser.add_argument("--synthetic", type=int, default=0,
                         help="Use N synthetic image/mask pairs instead of the dataset directories.")
     parser.add_argument("--dataset-root", type=str, default=".", help="Directory holding dataset/.")
+    parser.add_argument("--device_loader", action="store_true",
+                        help="Keep the decoded samples on the GPU as uint8 and build every batch there "
+                             "(same batches; no effect with --synthetic).")
     return parser.parse_args(argv)
 
 
@@ -141,11 +145,17 @@ def main(argv=None):
                                   shuffle=False, rank=rank, world=world)
         else:
             root = args.dataset_root
-            train = PairLoader(os.path.join(root, TRAIN_FRAMES_DIR), os.path.join(root, TRAIN_MASKS_DIR),
-                               TARGET_SIZE, args.batch_size, SEED, shuffle=True, horizontal_flip=True,
-                               rank=rank, world=world)
-            val = PairLoader(os.path.join(root, VAL_FRAMES_DIR), os.path.join(root, VAL_MASKS_DIR), TARGET_SIZE,
-                             args.batch_size, SEED, shuffle=False, horizontal_flip=False, rank=rank, world=world)
+            if args.device_loader:
+                from functools import partial
+                from unet_amd.device_data import DevicePairLoader
+                loader = partial(DevicePairLoader, device=f"cuda:{local}")
+            else:
+                loader = PairLoader
+            train = loader(os.path.join(root, TRAIN_FRAMES_DIR), os.path.join(root, TRAIN_MASKS_DIR),
+                           TARGET_SIZE, args.batch_size, SEED, shuffle=True, horizontal_flip=True,
+                           rank=rank, world=world)
+            val = loader(os.path.join(root, VAL_FRAMES_DIR), os.path.join(root, VAL_MASKS_DIR), TARGET_SIZE,
+                         args.batch_size, SEED, shuffle=False, horizontal_flip=False, rank=rank, world=world)
         say("Data Generators created successfully.")
     except Exception as e:  # reference: print + exit(1) (train.py:208-217)
         print("\n--- Error initializing ImageDataGenerator ---")

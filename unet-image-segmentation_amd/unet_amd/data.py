@@ -133,15 +133,21 @@ class PairLoader:
                 yield Shard(*self.load(idx[lo:hi], flips), global_size=len(idx))
             epoch += 1
 
-    def _sample(self, i, flip):
+    def _sample_u8(self, i, keep=True):
+        """Sample i decoded and resized, as uint8 (frame, mask); keep: enter it into the host cache
+        while the budget lasts."""
         xy = self._cache.get(i)
         if xy is None:
             xy = (load_image_u8(self.frames[i], self.size, "rgb"), load_image_u8(self.masks[i], self.size, "grayscale"))
             nb = xy[0].nbytes + xy[1].nbytes
             with self._lock:  # decode threads share the budget: check-and-add as one step
-                if i not in self._cache and self._cached_bytes + nb <= self.cache_bytes:
+                if keep and i not in self._cache and self._cached_bytes + nb <= self.cache_bytes:
                     self._cache[i] = xy
                     self._cached_bytes += nb
+        return xy
+
+    def _sample(self, i, flip):
+        xy = self._sample_u8(i)
         x = xy[0].astype(np.float32) / 255.0  # rescale=1/255 (reference scripts/train.py:170-178)
         y = xy[1].astype(np.float32) / 255.0
         if flip:
@@ -160,6 +166,23 @@ class PairLoader:
             pairs = [self._sample(int(i), bool(flips[i])) for i in idx]
         return (np.ascontiguousarray(np.stack([p[0] for p in pairs])),
                 np.ascontiguousarray(np.stack([p[1] for p in pairs])))
+
+
+def gather_u8_reference(src, slots):
+    """NumPy restatement of the batch-gather kernel (unet_batch_gather_u8, csrc/batch.hip): uint8
+    samples src (n, h, w, c) and b slot entries -> fp32 (b, h, w, c).  An entry e >= 0 takes sample e
+    as stored, e < 0 takes sample ~e mirrored along w; the decoded index is clamped to [0, n-1].
+    The values are PairLoader's own: a.astype(float32) / 255.0."""
+    src = np.asarray(src)
+    if src.dtype != np.uint8 or src.ndim != 4:
+        raise ValueError(f"src: expected uint8 (n, h, w, c), got {src.dtype} {src.shape}")
+    slots = np.asarray(slots).reshape(-1)
+    out = np.empty((len(slots),) + src.shape[1:], np.float32)
+    for i, e in enumerate(slots):
+        e = int(e)
+        a = src[min(max(~e if e < 0 else e, 0), src.shape[0] - 1)]
+        out[i] = (a[:, ::-1] if e < 0 else a).astype(np.float32) / 255.0
+    return out
 
 
 class synthetic_pairs:

@@ -1037,6 +1037,32 @@ def image_resize_u8(src: Tensor, ytab: Tensor, xtab: Tensor, out: Tensor, slot: 
     return out
 
 
+def batch_gather_u8(src: Tensor, slots: Tensor, out: Tensor) -> Tensor:
+    """Device-resident uint8 samples src (n, h, w, c), c = 1 or 3, and a device int32 slot table
+    (b,) -> the fp32 batch out (b, h, w, c): out[i] = src[e].float() / 255 for e = slots[i] >= 0, and
+    src[~e] mirrored along w for e < 0; bitwise data.gather_u8_reference(src, slots).  An entry
+    outside the cache is clamped into it on the device."""
+    _check_dt(src, "src", torch.uint8)
+    _check_dt(slots, "slots", torch.int32)
+    _check(out, "out")
+    if src.dim() != 4 or src.shape[3] not in (1, 3):
+        raise ValueError(f"src: expected (n, h, w, 1 or 3) samples, got {tuple(src.shape)}")
+    n, h, w, c = (int(v) for v in src.shape)
+    if slots.dim() != 1:
+        raise ValueError(f"slots: expected shape (b,), got {tuple(slots.shape)}")
+    b = int(slots.shape[0])
+    if tuple(out.shape) != (b, h, w, c):
+        raise ValueError(f"out: expected ({b}, {h}, {w}, {c}), got {tuple(out.shape)}")
+    if min(n, h, w, b) < 1:
+        raise ValueError(f"empty gather: {n} samples of {h}x{w}, {b} slots")
+    if h * w * c > 2 ** 31 - 1:
+        raise ValueError(f"a sample of {h}x{w}x{c} exceeds 2^31 bytes")
+    px = float(b * h * w * c)
+    _call("unet_batch_gather_u8", (px, 5.0 * px + 4.0 * b), _ptr(src), n, h, w, c, _ptr(slots), b, _ptr(out),
+          _stream())
+    return out
+
+
 def mask_resize(prob: Tensor, ytab: Tensor, xtab: Tensor, out: Tensor, threshold: float = 0.5) -> Tensor:
     """fp32 probabilities (h, w, ncls) of one image -> uint8 mask out (oh, ow): 255 where the
     bilinearly resized probability > threshold (ncls == 1), else the argmax class index; bitwise the

@@ -26,7 +26,8 @@ class _Failure:
 
 class Prefetcher:
     """Iterates `source` (yielding (x, y) numpy batches, optionally with .global_size) and yields
-    (x, y) device tensors (a `data.Shard` when the source batch carries global_size)."""
+    (x, y) device tensors (a `data.Shard` when the source batch carries global_size).  Batches that
+    are device tensors already pass through with their `.event`."""
 
     def __init__(self, source: Iterable, device=None, depth: int = 3, limit: Optional[int] = None):
         """limit: pull at most this many batches from `source` per iteration, so a single-pass
@@ -67,13 +68,22 @@ class Prefetcher:
                 taken += 1
                 x, y = batch[0], batch[1]
                 gsz = getattr(batch, "global_size", None)
-                xd, xp = self._to_device(x, stream)
-                yd, yp = self._to_device(y, stream)
-                ev = None
-                if stream is not None:
-                    ev = torch.cuda.Event()
-                    ev.record(stream)
-                item = (xd, yd, gsz, ev, (xp, yp))  # pinned buffers stay referenced until consumed
+                if isinstance(x, torch.Tensor) and x.is_cuda:
+                    # built on the device already (device_data.DevicePairLoader): passed through with
+                    # the event its producer recorded, or one on the stream this thread issues to
+                    ev = getattr(batch, "event", None)
+                    if ev is None:
+                        ev = torch.cuda.Event()
+                        ev.record(torch.cuda.current_stream(x.device))
+                    item = (x, y, gsz, ev, None)
+                else:
+                    xd, xp = self._to_device(x, stream)
+                    yd, yp = self._to_device(y, stream)
+                    ev = None
+                    if stream is not None:
+                        ev = torch.cuda.Event()
+                        ev.record(stream)
+                    item = (xd, yd, gsz, ev, (xp, yp))  # pinned buffers stay referenced until consumed
                 if not self._put(q, stop, item):
                     break
                 if self.limit is not None and taken >= self.limit:
