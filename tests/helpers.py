@@ -1,6 +1,8 @@
 """Shared test helpers (host <-> device, error metrics, oracle-side view restatements)."""
 from __future__ import annotations
 
+import functools
+
 import numpy as np
 
 from oracle import keras_ops as K
@@ -224,6 +226,98 @@ def bound_ratio(got, ref, bound):
     if d.size == 0:
         return 0.0
     return float(np.where(np.isnan(d), np.inf, d / bound).max())
+
+
+def randomised_stats(w, rng):
+    """A copy of a Keras-named float32 weight dict with non-trivial BN moving statistics, gamma and
+    beta, and biases."""
+    w = dict(w)
+    for k in w:
+        if k.endswith("moving_mean"):
+            w[k] = (rng.standard_normal(w[k].shape) * 0.2).astype(np.float32)
+        elif k.endswith("moving_variance"):
+            w[k] = (0.5 + rng.random(w[k].shape)).astype(np.float32)
+        elif k.endswith("gamma"):
+            w[k] = (1 + 0.2 * rng.standard_normal(w[k].shape)).astype(np.float32)
+        elif k.endswith("beta") or k.endswith("/bias"):
+            w[k] = (0.1 * rng.standard_normal(w[k].shape)).astype(np.float32)
+    return w
+
+
+def weights_with_stats(model, rng):
+    """Random Keras-initialised weights plus non-trivial BN moving stats / gamma / beta."""
+    w = randomised_stats(model.engine.get_weights_dict(), rng)
+    model.engine.set_weights_dict(w)
+    return {k: v.astype(np.float64) for k, v in w.items()}
+
+
+def host_batch(rng, n, cfg):
+    """NumPy float32 (x, y) of n images for a configuration: x uniform, y a random mask (one-hot for > 1 class)."""
+    size, ncls = cfg[0], cfg[1]
+    x = rng.random((n,) + tuple(size), dtype=np.float32)
+    if ncls == 1:
+        y = (rng.random((n,) + tuple(size[:2]) + (1,)) > 0.6).astype(np.float32)
+    else:
+        y = np.eye(ncls, dtype=np.float32)[rng.integers(0, ncls, (n,) + tuple(size[:2]))]
+    return x, y
+
+
+def batch(rng, n, cfg):
+    """host_batch on the device."""
+    import torch
+    x, y = host_batch(rng, n, cfg)
+    return torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
+
+
+HOST_LOOP_SIZE = (64, 64, 3)
+HOST_LOOP_VAL_BATCHES = (2, 2, 2, 3)  # three validation batches of 2 images and one extra, of another size
+
+
+@functools.lru_cache(maxsize=None)
+def host_loop_case(ncls, use_bn=True, seed=11):
+    """What the validation tests of the host loop share, computed once and without a device: the
+    weights of UNetModel(seed=seed) with randomised_stats (float32, and as float64 for the oracle),
+    the validation batches (NumPy), the float64 oracle's inference probabilities of each, and for the
+    binary head the MeanIoU threshold: the median of those probabilities over the first three batches,
+    rounded to float32 (the metric kernel's threshold argument is a float, so the oracle and the kernel
+    compare against the same number).  A freshly initialised binary head puts every pixel within about
+    0.003 of one value, all on one side of 0.5: a MeanIoU at 0.5 would fill one column of the confusion
+    matrix and could not tell swapped indices.  Nothing in the returned dict may be written to."""
+    from oracle.unet_ref import UNetOracle
+    from unet_amd.params import init_weights, unet_variables
+    cfg = (HOST_LOOP_SIZE, ncls, use_bn, 0.2, {})
+    rng = np.random.default_rng(9000 + 10 * ncls + use_bn)
+    w32 = randomised_stats(init_weights(unet_variables(HOST_LOOP_SIZE[2], ncls, use_bn), seed), rng)
+    w64 = {k: v.astype(np.float64) for k, v in w32.items()}
+    batches = [host_batch(rng, n, cfg) for n in HOST_LOOP_VAL_BATCHES]
+    orc = UNetOracle(ncls, 0.2, use_bn)
+    probs = [orc.forward(w64, x.astype(np.float64), training=False)[0] for x, _ in batches]
+    thr = float(np.float32(np.median(np.concatenate([p.ravel() for p in probs[:3]])))) if ncls == 1 else None
+    for a in [*w64.values(), *probs]:
+        a.setflags(write=False)
+    return {"cfg": cfg, "seed": seed, "w32": w32, "w64": w64, "batches": batches, "probs": probs, "threshold": thr}
+
+
+def oracle_values(y, prob):
+    """[dice_loss, dice_coef, iou_coef] of the oracle, as UNetModel.test_step orders them."""
+    y = np.asarray(y, np.float64)
+    return np.array([K.dice_loss(y, prob), K.dice_coef(y, prob), K.iou_coef(y, prob)])
+
+
+SCRIPTED_MONITOR = (0.5, 0.7, 0.6, 0.6, 0.6)
+
+
+def scripted_monitor_callback(values=SCRIPTED_MONITOR, key="val_mean_io_u"):
+    """A callback that overwrites logs[key] with values[epoch].  CallbackList hands every callback the
+    same dict, so the callbacks after it in the list see a monitored trajectory that is known without
+    a device, while the weights, files and learning rates they act on are the model's own."""
+    from unet_amd.callbacks import Callback
+
+    class Scripted(Callback):
+        def on_epoch_end(self, epoch, logs=None):
+            logs[key] = values[epoch]
+
+    return Scripted()
 
 
 def dev(a):

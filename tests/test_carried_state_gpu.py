@@ -19,22 +19,12 @@ import pytest
 
 from helpers import (TRACE_CONFIGS, bound_ratio, engine_state, fresh_model, fresh_step, host, record_launches, rel_err,
                      set_routes, step_outputs, trace_model)
+from helpers import batch as _batch
 from oracle import keras_ops as K
 from oracle.unet_ref import UNetOracle
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
-
-
-def _batch(rng, n, cfg):
-    """Device (x, y) of n images for a configuration: x uniform, y a random mask (one-hot for > 1 class)."""
-    size, ncls = cfg[0], cfg[1]
-    x = rng.random((n,) + tuple(size), dtype=np.float32)
-    if ncls == 1:
-        y = (rng.random((n,) + tuple(size[:2]) + (1,)) > 0.6).astype(np.float32)
-    else:
-        y = np.eye(ncls, dtype=np.float32)[rng.integers(0, ncls, (n,) + tuple(size[:2]))]
-    return torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
 
 
 def _assert_same(cont, fresh, what):

@@ -66,6 +66,26 @@ def test_dp_sync_bn_equals_full_batch(global_batch, drop):
 
 
 @pytest.mark.gpu
+def test_dp_two_ranks_agree_on_the_validation_monitor():
+    """tools/dp_eval_check.py: evaluate on shards 3+2 of two global batches of 5.  Every rank's
+    val_mean_io_u is exactly that of the ranks' confusion matrices summed (each from its own device
+    probabilities) and identical across the ranks -- the callbacks that monitor it then decide alike --
+    the training counts are back in the metric afterwards, and the rank-local val_loss is the shard's own."""
+    env = dict(os.environ)
+    if torch.cuda.device_count() < 2:
+        env["UNET_DP_ONE_DEVICE"] = "1"
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
+           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
+           os.path.join(ROOT, "tools", "dp_eval_check.py")]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "val_mean_io_u identical across ranks: True" in r.stdout
+    assert r.stdout.count("equal to summed confusion: True") == 2, r.stdout[-2000:]
+    assert r.stdout.count("training confusion restored: True") == 2, r.stdout[-2000:]
+    assert r.stdout.count("equal to own shard: True") == 2, r.stdout[-2000:]
+
+
+@pytest.mark.gpu
 def test_bench_gpus_flag_spawns_ranks():
     """`python bench.py --gpus 2` (the driver's command shape, no launcher environment) runs two
     ranks: the parent starts torch.distributed.run as a child before touching the GPU, and the

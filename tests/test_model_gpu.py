@@ -16,26 +16,11 @@ import numpy as np
 import pytest
 
 from helpers import f32, host, norm_err, rel_err
+from helpers import weights_with_stats as _weights_with_stats
 from oracle.unet_ref import UNetOracle
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
-
-
-def _weights_with_stats(model, rng):
-    """Random Keras-initialised weights plus non-trivial BN moving stats / gamma / beta."""
-    w = model.engine.get_weights_dict()
-    for k in w:
-        if k.endswith("moving_mean"):
-            w[k] = (rng.standard_normal(w[k].shape) * 0.2).astype(np.float32)
-        elif k.endswith("moving_variance"):
-            w[k] = (0.5 + rng.random(w[k].shape)).astype(np.float32)
-        elif k.endswith("gamma"):
-            w[k] = (1 + 0.2 * rng.standard_normal(w[k].shape)).astype(np.float32)
-        elif k.endswith("beta") or k.endswith("/bias"):
-            w[k] = (0.1 * rng.standard_normal(w[k].shape)).astype(np.float32)
-    model.engine.set_weights_dict(w)
-    return {k: v.astype(np.float64) for k, v in w.items()}
 
 
 def _data(rng, n, h, w, ncls):

@@ -80,9 +80,12 @@ class UNetModel:
         With sync_bn on, every training-mode forward (train_step, engine.forward(training=True),
         model(x, training=True)) issues one blocking all-gather per BatchNorm and every backward
         one all-reduce per BatchNorm, on the main stream: ALL ranks of the group must run them
-        together, in the same order, or the group hangs.  Inference (predict / evaluate,
-        training=False) uses the moving statistics and issues no collective, so it may run on
-        one rank alone."""
+        together, in the same order, or the group hangs.  The inference forward (predict,
+        test_step, training=False) uses the moving statistics and issues no collective, so it
+        may run on one rank alone.  evaluate (and so fit's validation) with a MeanIoU metric
+        compiled in IS a collective: it sums the confusion matrix over `group`, so that every
+        rank logs the same value and the callbacks that monitor it decide alike; every rank
+        must call it.  Its loss and coefficients stay this rank's own."""
         import torch.distributed as dist
         self.bucketer = GradBucketer(self.engine.grads, bucket_bytes, group)
         self.engine.grad_hook = self.bucketer.ready
@@ -218,7 +221,7 @@ class UNetModel:
                 nsteps += 1
             logs = self._log_values(acc / nsteps)
             if self.mean_iou is not None:
-                self.mean_iou.all_reduce()
+                self.mean_iou.all_reduce(self._dp_group())
                 logs[self.mean_iou.name] = self.mean_iou.result()
             self.sync_bn_statistics()
             if validation_data is not None:
@@ -258,7 +261,15 @@ class UNetModel:
         if self.bucketer is not None and self.bucketer.world > 1:
             average_(self.engine.stats, self.bucketer.group)
 
+    def _dp_group(self):
+        """The process group of enable_data_parallel (None: the default group)."""
+        return self.bucketer.group if self.bucketer is not None else None
+
     def evaluate(self, data, steps: Optional[int] = None, prefix: str = "") -> Dict[str, float]:
+        """Mean of test_step's [loss, dice_coef, iou_coef] over `steps` batches (the unweighted
+        mean of the batch means) and MeanIoU over their confusion matrix, keys prefixed.  The
+        training confusion counts are put back afterwards.  Data parallel: a collective when a
+        MeanIoU is compiled in (see enable_data_parallel)."""
         it = iter(self._prefetch(data, steps or 1))
         if self.mean_iou is not None:
             saved = self.mean_iou.confusion.clone()
@@ -273,7 +284,7 @@ class UNetModel:
             it.close()
         logs = self._log_values(acc / n, prefix)
         if self.mean_iou is not None:
-            self.mean_iou.all_reduce()
+            self.mean_iou.all_reduce(self._dp_group())
             logs[prefix + self.mean_iou.name] = self.mean_iou.result()
             self.mean_iou.confusion.copy_(saved)
         return logs
