@@ -219,7 +219,9 @@ int unet_sepconv_fwd(const unet_view* x, int n, int h, int w, const float* dw_ke
  * gamma's sign and fmaf / relu are monotone, so a BNRELU view of z_pool_sel reads exactly the
  * pooled activation, one value per output pixel instead of four.  Written by the kernel's
  * epilogue (register-A schedule) or by unet_pool_select after it.  The max-pool BACKWARD still
- * routes through z (first maximum of the window): POOL_BNRELU views of z.                   */
+ * routes through z (first maximum of the window): POOL_BNRELU views of z.
+ * unet_pool_select: h and w even; c % 4 == 0 reads channel quads (z, out, gamma 16-B aligned),
+ * any other c one channel per thread.                                                       */
 int unet_pool_select(const float* z, int n, int h, int w, int c, const float* gamma,
                      float* out, unet_stream_t stream);
 /* Kernel schedule of unet_sepconv_fwd (process-wide; returns the previous value, < 0 on a bad

@@ -83,6 +83,30 @@ TRACE_DEFAULTS = {"overlap": True, "fuse_block_bwd": True, "recompute_y": True, 
                   "fuse_min_pixels": 64 * 64, "fuse_min_total": 16 * 1024, "graph_predict": False}
 
 
+# Networks off the default filters and the square 3- or 4-channel input: name -> (input size, filters,
+# classes, BatchNorm, dropout, fuse_sepconv, batch).  What each one reaches that nothing else does is
+# pinned, without a device, by tests/test_geometry_plan_host.py (GEOMETRY_REACHES there).
+GEOMETRIES = {
+    "two64": ((32, 64, 3), (64, 64), 1, True, 0.2, "always", 2),
+    "two64_nodrop": ((32, 64, 3), (64, 64), 1, True, 0.0, "always", 2),
+    "two64_auto": ((128, 128, 3), (64, 64), 1, True, 0.2, "auto", 2),
+    "gray3264": ((32, 64, 1), (32, 64), 1, True, 0.2, "always", 2),
+    "thin": ((32, 48, 3), (16, 32), 3, True, 0.2, "auto", 3),
+    "mult8": ((32, 64, 3), (24, 40), 1, True, 0.0, "always", 2),
+    "wide80": ((32, 64, 3), (80, 144), 2, True, 0.2, "always", 2),
+    "not4": ((16, 32, 3), (8, 10), 1, True, 0.2, "auto", 2),
+    "deep5": ((64, 32, 3), (8, 16, 32, 64, 128), 1, False, 0.2, "always", 1),
+    "one_level": ((16, 32, 5), (64,), 1, True, 0.2, "always", 3),
+}
+
+
+def geometry_cfg(name):
+    """(cfg, filters, batch) of a GEOMETRIES entry: cfg as trace_model / fresh_step / host_batch take it,
+    its engine attributes pinning fuse_sepconv."""
+    size, filters, ncls, bn, drop, fuse, n = GEOMETRIES[name]
+    return (size, ncls, bn, drop, {"fuse_sepconv": fuse}), filters, n
+
+
 def step_trace(cid):
     """The launch trace of configuration `cid`: one warm-up train step (predict for P), then the
     recorded second one, on a fresh model."""
@@ -139,22 +163,24 @@ def set_routes(model, attrs):
         setattr(model.engine, k, v)
 
 
-def trace_model(cfg, optimizer=None, metrics=None, seed=2301, attrs=None):
+def trace_model(cfg, optimizer=None, metrics=None, seed=2301, attrs=None, filters=None):
     """A new model of configuration cfg = (input size, classes, BatchNorm, dropout, engine attributes)
     -- a TRACE_CONFIGS value -- with the routes pinned (attrs replaces the configuration's own) and an
-    AdamW of the given get_config() (default: the traces' 2e-3, 1e-4) compiled in for the dice loss."""
+    AdamW of the given get_config() (default: the traces' 2e-3, 1e-4) compiled in for the dice loss.
+    filters: the network's widths (default: the reference's)."""
     from unet_amd.model import UNetModel
     from unet_amd.optim import AdamW
     size, ncls, bn, drop, cattrs = cfg
-    model = UNetModel(size, ncls, dropout_rate=drop, use_batch_norm=bn, device="cuda:0", seed=seed)
+    kw = {} if filters is None else {"filters": tuple(filters)}
+    model = UNetModel(size, ncls, dropout_rate=drop, use_batch_norm=bn, device="cuda:0", seed=seed, **kw)
     set_routes(model, cattrs if attrs is None else attrs)
     model.compile(AdamW(**(optimizer or dict(learning_rate=2e-3, weight_decay=1e-4))), "dice_loss", metrics)
     return model
 
 
-def fresh_model(cfg, state, metrics=None, seed=2301, attrs=None):
+def fresh_model(cfg, state, metrics=None, seed=2301, attrs=None, filters=None):
     """trace_model with `state` loaded: a new engine that knows the visible state and nothing else."""
-    model = trace_model(cfg, state["config"], metrics, seed, attrs)
+    model = trace_model(cfg, state["config"], metrics, seed, attrs, filters)
     load_engine_state(model, state)
     return model
 
@@ -168,11 +194,11 @@ def step_outputs(model, res, n):
             "params": eng.params.clone(), "stats": eng.stats.clone(), "m": opt._m.clone(), "v": opt._v.clone()}
 
 
-def fresh_step(cfg, state, x, y, metrics=None, seed=2301, attrs=None):
+def fresh_step(cfg, state, x, y, metrics=None, seed=2301, attrs=None, filters=None):
     """One train step of a fresh model (fresh_model) on (x, y) from `state`, with empty workspaces
     for the call; returns step_outputs."""
     from unet_amd import ops
-    model = fresh_model(cfg, state, metrics, seed, attrs)
+    model = fresh_model(cfg, state, metrics, seed, attrs, filters)
     ws, ops.WORKSPACE = ops.WORKSPACE, ops._Workspace()
     try:
         res = model.train_step(x, y)
@@ -367,3 +393,178 @@ def view_value(mode, src0, sc0=None, sh0=None, src1=None, sc1=None, sh1=None, dr
     if drop_rate > 0:
         x = x * K.dropout_mult(drop_seed, x.shape, drop_rate, np.float64)
     return x
+
+
+# ------------------------------------------------------- one train step against the oracle ------
+def oracle_preacts(cache, p, use_bn, names):
+    """name -> the float64 oracle's pre-activation (BatchNorm output, or z + bias) of each block of a
+    training forward's cache."""
+    out = {}
+    for name in names:
+        rec = cache[name]
+        if use_bn:
+            inv = p[f"{name}_bn/gamma"] / np.sqrt(rec["var"] + 1e-3)
+            out[name] = rec["z"] * inv + (p[f"{name}_bn/beta"] - rec["mean"] * inv)
+        else:
+            out[name] = rec["z"] + p[f"{name}_sepconv/bias"]
+    return out
+
+
+def engine_preacts(engine):
+    """name -> the device's pre-activation z * scale + shift of each block of the last training forward."""
+    A = engine._acts_last
+    out = {}
+    for b in engine.blocks:
+        bb = A.blocks[b.name]
+        out[b.name] = (bb.z.cpu().double() * bb.scale.cpu().double() + bb.shift.cpu().double()).numpy()
+    return out
+
+
+def same_decisions(pre_a, pre_b):
+    """True if two forwards (name -> pre-activation) made the same ReLU-mask decisions in every block
+    and the same 2x2 max-pool argmax decisions after every encoder stage."""
+    for name, a in pre_a.items():
+        b = pre_b[name]
+        if not np.array_equal(a > 0, b > 0):
+            return False
+        if name.startswith("enc") and name.endswith("block2"):
+            args = []
+            for pre in (a, b):
+                N, H, W, C = pre.shape
+                win = np.maximum(pre, 0).reshape(N, H // 2, 2, W // 2, 2, C).transpose(0, 1, 3, 5, 2, 4).reshape(-1, 4)
+                args.append(np.where(win.max(1) > 0, win.argmax(1), -1))
+            if not np.array_equal(args[0], args[1]):
+                return False
+    return True
+
+
+def discrete_decisions_agree(engine, cache, p, use_bn):
+    """True if the device forward made the same ReLU-mask and 2x2 max-pool argmax decisions as
+    the float64 oracle.  Where a pre-activation or a pool near-tie sits within fp32 rounding of
+    the decision boundary, the decision - and so where the gradient flows - is set by rounding:
+    a discontinuity no fp32 implementation can match an fp64 oracle on.  Parity of gradients is
+    only well posed on inputs whose decisions agree."""
+    return same_decisions(engine_preacts(engine), oracle_preacts(cache, p, use_bn, [b.name for b in engine.blocks]))
+
+
+MAX_INPUT_DRAWS = 10  # a condition of the parity tests, not a tuning knob
+
+
+def train_step_parity(model, orc, draw, loss="dice_loss", lr=2e-3, wd=1e-4):
+    """One train step of `model` against the float64 oracle `orc`, with the project's gates: loss and
+    dice within 1e-5; every gradient's relative L2 error <= max(1e-3, 2 x the float32 oracle's own);
+    the gradient key sets equal; post-AdamW weights and moving statistics within 1e-4 relative.
+
+    draw(attempt) -> (p, x, y): float64 weights already loaded into the model, and a NumPy batch; it is
+    called again (at most MAX_INPUT_DRAWS times) until the ReLU / max-pool decisions of the device
+    agree with float64 (discrete_decisions_agree).  Returns {"input_draws", and the worst error / gate
+    ratio of each gate} after asserting every gate."""
+    import pytest
+    import torch
+    from unet_amd.optim import AdamW
+    use_bn, drop = orc.use_bn, orc.dropout_rate
+    okind = "dice" if loss == "dice_loss" else "iou"
+    for attempt in range(MAX_INPUT_DRAWS):
+        p, x, y = draw(attempt)
+        model.compile(AdamW(learning_rate=lr, weight_decay=wd), loss)
+        seeds = model.engine.drop_seeds(model.engine.step_count + 1)
+        res = model.train_step(x, y).cpu().numpy()
+        torch.cuda.synchronize()
+        grads = {k: host(t) for k, t in model.engine.gvars.items()}
+        neww = model.engine.get_weights_dict()
+        _, cache, _ = orc.forward(p, x.astype(np.float64), training=True, drop_seeds=seeds if drop > 0 else None)
+        if discrete_decisions_agree(model.engine, cache, p, use_bn):
+            break
+    else:
+        pytest.fail("no inputs found whose ReLU / max-pool decisions are not decided by rounding")
+    # (the oracle's whole step only for the draw that is compared)
+    opt = {k: (np.zeros_like(v), np.zeros_like(v)) for k, v in p.items() if k in grads}
+    lval, dice, g, newp, _, prob = orc.train_step(p, opt, x.astype(np.float64), y.astype(np.float64), 1, lr, wd,
+                                                  drop_seeds=seeds if drop > 0 else None, loss=okind)
+    out = {"input_draws": attempt + 1, "loss": abs(res[0] - lval) / 1e-5, "dice": abs(res[1] - dice) / 1e-5}
+    print(f"train_step_parity: input draws = {attempt + 1}, loss {res[0]:.7f} (oracle {lval:.7f})")
+    assert abs(res[0] - lval) < 1e-5, (res[0], lval)
+    assert abs(res[1] - dice) < 1e-5
+    # fp32 conditioning reference: the same oracle step in float32
+    p32 = {k: v.astype(np.float32) for k, v in p.items()}
+    prob32, cache32, _ = orc.forward(p32, x, training=True, drop_seeds=seeds if drop > 0 else None)
+    _, dprob32 = orc.loss_and_dprob(y, prob32, okind)
+    g32, _ = orc.backward(p32, cache32, dprob32)
+    bad = {}
+    rows = []
+    for k in g:
+        e = norm_err(grads[k], g[k])
+        e32 = norm_err(g32[k], g[k])
+        tol = max(1e-3, 2.0 * e32)
+        rows.append((e, e32, k))
+        if not e <= tol:
+            bad[k] = (e, tol)
+    out["grad"] = max(e / max(1e-3, 2.0 * e32) for e, e32, _ in rows)
+    out["grad_worst"] = max(rows, key=lambda r: r[0] / max(1e-3, 2.0 * r[1]))[2]
+    if bad:
+        print(f"attempt {attempt}")
+        for e, e32, k in sorted(rows)[:8] + sorted(rows)[-8:]:
+            print(f"{k:45s} hip {e:.3e}  fp32-oracle {e32:.3e}")
+    assert not bad, sorted(bad.items())[:6]
+    assert set(g) == set(grads)
+    stat = {s.name for s in model.engine.specs if not s.trainable}
+    out["weights"] = out["stats"] = 0.0
+    for k, v in newp.items():
+        e = rel_err(neww[k], v)
+        which = "stats" if k in stat else "weights"
+        out[which] = max(out[which], e / 1e-4)
+        assert e < 1e-4, k
+    return out
+
+
+# Seed base of each geometry's input draws (draw k uses base + 1000 k), chosen on the CPU alone: the
+# first base of 5000, 5001, ... at which the float32 oracle's ReLU / max-pool decisions of draw 0 agree
+# with float64's (geometry_oracle32_agrees).  two64_auto is the exception: at 128 x 128 (21 M decisions,
+# the closest within 1e-7 .. 4e-7 of its boundary in float64 on the 64 bases looked at) the float32
+# NumPy oracle agrees with float64 on none of the bases 5000..5999 in draws 0..2, so no base can be
+# chosen that way and it keeps the first candidate, 5000.  The device's own draw count is what the
+# GPU test records (two64_auto: 7 of the 10 allowed on an MI355X; every other geometry 1).
+GEOMETRY_SEEDS = {
+    "two64": 5004,
+    "two64_nodrop": 5003,
+    "two64_auto": 5000,
+    "gray3264": 5001,
+    "thin": 5000,
+    "mult8": 5000,
+    "wide80": 5009,
+    "not4": 5000,
+    "deep5": 5001,
+    "one_level": 5001,
+}
+GEOMETRY_ENGINE_SEED = 2301  # (trace_model's default: fresh_step builds the same dropout stream)
+
+
+def geometry_draw(name, attempt, base=None):
+    """Draw `attempt` of a geometry: (float32 Keras-named weights -- the initial ones of
+    UNetModel(seed=GEOMETRY_ENGINE_SEED) with randomised_stats --, x, y), without a device."""
+    from unet_amd.params import init_weights, unet_variables
+    cfg, filters, n = geometry_cfg(name)
+    size, ncls, bn = cfg[0], cfg[1], cfg[2]
+    rng = np.random.default_rng((GEOMETRY_SEEDS[name] if base is None else base) + 1000 * attempt)
+    w32 = randomised_stats(init_weights(unet_variables(size[2], ncls, bn, filters), GEOMETRY_ENGINE_SEED), rng)
+    return (w32,) + host_batch(rng, n, cfg)
+
+
+def geometry_oracle32_agrees(name, attempt, base=None):
+    """True if the float32 oracle's training forward of draw `attempt` makes the ReLU / max-pool
+    decisions of the float64 one (step attempt + 1 of the engine's dropout stream)."""
+    from oracle.unet_ref import UNetOracle
+    from unet_amd.engine import _mix64, drop_sites
+    cfg, filters, _ = geometry_cfg(name)
+    _, ncls, bn, drop, _ = cfg
+    w32, x, _ = geometry_draw(name, attempt, base)
+    seeds = {s: _mix64(GEOMETRY_ENGINE_SEED, attempt + 1, i + 1) for i, s in enumerate(drop_sites(len(filters)))}
+    orc = UNetOracle(ncls, drop, bn, filters)
+    pre = []
+    for dt in (np.float64, np.float32):
+        p = {k: v.astype(dt) for k, v in w32.items()}
+        _, cache, _ = orc.forward(p, x.astype(dt), training=True, drop_seeds=seeds if drop > 0 else None)
+        names = [k for k in cache if k.endswith("block1") or k.endswith("block2")]
+        pre.append(oracle_preacts(cache, p, bn, names))
+    return same_decisions(pre[1], pre[0])
+

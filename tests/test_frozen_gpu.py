@@ -33,16 +33,20 @@ from unet_amd import frozen  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 F = (64, 128, 256, 512)
-# name -> (classes, input shape, weight seed, input seed, use_batch_norm)
+# name -> (classes, input shape, weight seed, input seed, use_batch_norm, filters)
 CASES = {
-    "c1_2x32x32": (1, (2, 32, 32, 3), 11, 21, True),
-    "c3_3x48x32": (3, (3, 48, 32, 3), 2301, 7, True),   # tile levels 48x32, 24x16; rows 12x8, 6x4, 3x2
-    "c1_1x16x16": (1, (1, 16, 16, 3), 11, 21, True),    # the bottleneck is 1x1
-    "nobn_2x32x32": (1, (2, 32, 32, 3), 11, 21, False),  # case 1 as a no-BN model: the bias route
+    "c1_2x32x32": (1, (2, 32, 32, 3), 11, 21, True, F),
+    "c3_3x48x32": (3, (3, 48, 32, 3), 2301, 7, True, F),   # tile levels 48x32, 24x16; rows 12x8, 6x4, 3x2
+    "c1_1x16x16": (1, (1, 16, 16, 3), 11, 21, True, F),    # the bottleneck is 1x1
+    "nobn_2x32x32": (1, (2, 32, 32, 3), 11, 21, False, F),  # case 1 as a no-BN model: the bias route
+    # two levels off the default widths: a 32-output image block on a non-square input ...
+    "f3264_2x32x64": (1, (2, 32, 64, 3), 11, 21, True, (32, 64)),
+    # ... and widths 96 and 192: N tails in the tile (48x32, 24x16) and rows (12x8) policies
+    "f6496_3x48x32": (3, (3, 48, 32, 3), 2301, 7, True, (64, 96)),
 }
 
 
-def _weights(ncls, wseed, use_bn):
+def _weights(ncls, wseed, use_bn, F=F):
     w = MG.model_weights(ncls, F, wseed)
     if use_bn:
         return w
@@ -58,8 +62,8 @@ def _weights(ncls, wseed, use_bn):
 @functools.lru_cache(maxsize=None)
 def _reference(case):
     """(weights, x, float64 oracle activations, emulator activations), computed once per case."""
-    ncls, shape, wseed, xseed, use_bn = CASES[case]
-    w = _weights(ncls, wseed, use_bn)
+    ncls, shape, wseed, xseed, use_bn, F = CASES[case]
+    w = _weights(ncls, wseed, use_bn, F)
     x = MG.U(xseed, shape)
     ref = E.oracle_activations(w, x, ncls, F, use_bn)
     emu = E.forward(frozen.fold_weights(w, ncls, use_bn, F), x, ncls, F)
@@ -67,7 +71,7 @@ def _reference(case):
 
 
 def _frozen(case):
-    ncls, shape, _, _, use_bn = CASES[case]
+    ncls, shape, _, _, use_bn, F = CASES[case]
     w, x, _, _ = _reference(case)
     net = frozen.FrozenUNet(frozen.fold_weights(w, ncls, use_bn, F), shape[1:], ncls, F, "cuda:0")
     return net, torch.as_tensor(x.astype(np.float32), device="cuda:0")
@@ -75,6 +79,7 @@ def _frozen(case):
 
 @pytest.mark.parametrize("case", list(CASES))
 def test_every_layer_within_the_emulator_gate(case):
+    F = CASES[case][5]
     net, xt = _frozen(case)
     _, _, ref, emu = _reference(case)
     prob = net.forward(xt, keep_activations=True)

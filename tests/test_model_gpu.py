@@ -15,7 +15,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import f32, host, norm_err, rel_err
+from helpers import f32, train_step_parity
 from helpers import weights_with_stats as _weights_with_stats
 from oracle.unet_ref import UNetOracle
 
@@ -33,37 +33,6 @@ def _data(rng, n, h, w, ncls):
     else:
         y = np.eye(ncls, dtype=np.float32)[rng.integers(0, ncls, (n, h, w))]
     return x, y
-
-
-def discrete_decisions_agree(engine, cache, p, use_bn):
-    """True if the device forward made the same ReLU-mask and 2x2 max-pool argmax decisions as
-    the float64 oracle.  Where a pre-activation or a pool near-tie sits within fp32 rounding of
-    the decision boundary, the decision - and so where the gradient flows - is set by rounding:
-    a discontinuity no fp32 implementation can match an fp64 oracle on.  Parity of gradients is
-    only well posed on inputs whose decisions agree."""
-    A = engine._acts_last
-    for b in engine.blocks:
-        bb = A.blocks[b.name]
-        pre_h = (bb.z.cpu().double() * bb.scale.cpu().double() + bb.shift.cpu().double()).numpy()
-        rec = cache[b.name]
-        if use_bn:
-            inv = p[f"{b.name}_bn/gamma"] / np.sqrt(rec["var"] + 1e-3)
-            pre_o = rec["z"] * inv + (p[f"{b.name}_bn/beta"] - rec["mean"] * inv)
-        else:
-            pre_o = rec["z"] + p[f"{b.name}_sepconv/bias"]
-        if not np.array_equal(pre_h > 0, pre_o > 0):
-            return False
-        if b.name.startswith("enc") and b.name.endswith("block2"):
-            for pre in (pre_h, pre_o):
-                N, H, W, C = pre.shape
-                a = np.maximum(pre, 0).reshape(N, H // 2, 2, W // 2, 2, C).transpose(0, 1, 3, 5, 2, 4)
-                a = a.reshape(-1, 4)
-                arg = np.where(a.max(1) > 0, a.argmax(1), -1)
-                if pre is pre_h:
-                    arg_h = arg
-            if not np.array_equal(arg_h, arg):
-                return False
-    return True
 
 
 def test_builder_api_and_inference_parity_cfg1():
@@ -107,7 +76,6 @@ def test_train_step_parity(ncls, use_bn, drop, loss, fuse, record_property):
     "+r128": the 128-output blocks keep no y either (their weight gradients recompute it, through
     dec2_block1's dropout view)."""
     from unet_amd.model import UNetModel
-    from unet_amd.optim import AdamW
     n, hw = 2, 32
     model = UNetModel((hw, hw, 3), ncls, dropout_rate=drop, use_batch_norm=use_bn, seed=11)
     if fuse.endswith("+r128"):
@@ -116,58 +84,21 @@ def test_train_step_parity(ncls, use_bn, drop, loss, fuse, record_property):
     model.engine.fuse_sepconv = fuse
     model.engine.fuse_bn_bwd = fuse != "never"  # "never": also the separate BN-backward dz pass
     orc = UNetOracle(ncls, drop, use_bn)
-    lr, wd = 2e-3, 1e-4
-    okind = "dice" if loss == "dice_loss" else "iou"
-    for attempt in range(10):
+
+    def draw(attempt):
         rng = np.random.default_rng(ncls * 13 + int(drop * 10) + use_bn + 1000 * attempt)
         p = _weights_with_stats(model, rng)
-        x, y = _data(rng, n, hw, hw, ncls)
-        model.compile(AdamW(learning_rate=lr, weight_decay=wd), loss)
-        seeds = model.engine.drop_seeds(model.engine.step_count + 1)
-        res = model.train_step(x, y).cpu().numpy()
-        torch.cuda.synchronize()
-        grads = {k: host(t) for k, t in model.engine.gvars.items()}
-        neww = model.engine.get_weights_dict()
-        opt = {k: (np.zeros_like(v), np.zeros_like(v)) for k, v in p.items() if k in grads}
-        lval, dice, g, newp, _, prob = orc.train_step(p, opt, x.astype(np.float64), y.astype(np.float64), 1, lr, wd,
-                                                      drop_seeds=seeds if drop > 0 else None, loss=okind)
-        _, cache, _ = orc.forward(p, x.astype(np.float64), training=True, drop_seeds=seeds if drop > 0 else None)
-        if discrete_decisions_agree(model.engine, cache, p, use_bn):
-            break
-    else:
-        pytest.fail("no inputs found whose ReLU / max-pool decisions are not decided by rounding")
+        return (p,) + _data(rng, n, hw, hw, ncls)
+
+    out = train_step_parity(model, orc, draw, loss)
     # how many input draws it took to find one whose discrete decisions all agree with fp64
-    record_property("input_draws", attempt + 1)
-    print(f"train_step_parity[{ncls},{use_bn},{drop},{loss},{fuse}]: input draws = {attempt + 1}")
+    record_property("input_draws", out["input_draws"])
+    print(f"train_step_parity[{ncls},{use_bn},{drop},{loss},{fuse}]: input draws = {out['input_draws']}")
     log = os.environ.get("UNET_PARITY_LOG")
     if log:
         with open(log, "a") as f:
             f.write(json.dumps({"test": f"train_step_parity[{ncls},{use_bn},{drop},{loss},{fuse}]",
-                                "input_draws": attempt + 1}) + "\n")
-    assert abs(res[0] - lval) < 1e-5, (res[0], lval)
-    assert abs(res[1] - dice) < 1e-5
-    # fp32 conditioning reference: the same oracle step in float32
-    p32 = {k: v.astype(np.float32) for k, v in p.items()}
-    prob32, cache32, _ = orc.forward(p32, x, training=True, drop_seeds=seeds if drop > 0 else None)
-    _, dprob32 = orc.loss_and_dprob(y, prob32, okind)
-    g32, _ = orc.backward(p32, cache32, dprob32)
-    bad = {}
-    rows = []
-    for k in g:
-        e = norm_err(grads[k], g[k])
-        e32 = norm_err(g32[k], g[k])
-        tol = max(1e-3, 2.0 * e32)
-        rows.append((e, e32, k))
-        if e > tol:
-            bad[k] = (e, tol)
-    if bad:
-        print(f"attempt {attempt}")
-        for e, e32, k in sorted(rows)[:8] + sorted(rows)[-8:]:
-            print(f"{k:45s} hip {e:.3e}  fp32-oracle {e32:.3e}")
-    assert not bad, sorted(bad.items())[:6]
-    assert set(g) == set(grads)
-    for k, v in newp.items():
-        assert rel_err(neww[k], v) < 1e-4, k
+                                "input_draws": out["input_draws"]}) + "\n")
 
 
 def test_determinism_bitwise():

@@ -1037,7 +1037,8 @@ def _pool_ref(a):
     return a.reshape(N, H // 2, 2, W // 2, 2, C).max((2, 4))
 
 
-@pytest.mark.parametrize("n,h,w,c", [(2, 8, 16, 64), (1, 16, 32, 128), (3, 4, 6, 8)])
+@pytest.mark.parametrize("n,h,w,c", [(2, 8, 16, 64), (1, 16, 32, 128), (3, 4, 6, 8),
+                                     (2, 8, 16, 10), (1, 2, 2, 3), (3, 34, 18, 7)])  # c % 4 != 0: scalar lanes; > 1 block
 def test_pool_select(ops, n, h, w, c):
     """unet_pool_select: a BN+ReLU view of the selection reads bitwise the 2x2 max-pool of the BN+ReLU
     view of z (MaxPooling2D, model/u_net.py:69), for gammas of either sign (and +-0) and without BN."""

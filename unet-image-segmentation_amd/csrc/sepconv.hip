@@ -372,6 +372,21 @@ __global__ __launch_bounds__(256) void pool_select_kernel(const float* __restric
     }
 }
 
+// ... one channel per thread: channel counts that are no multiple of 4 (rows of z off the 16-B boundary)
+__global__ __launch_bounds__(256) void pool_select_scalar_kernel(const float* __restrict__ z, int64_t elems, int H2, int W2,
+                                                                 int C, const float* __restrict__ gamma,
+                                                                 float* __restrict__ out) {
+    for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < elems; e += (int64_t)gridDim.x * 256) {
+        const int ch = (int)(e % C);
+        const int64_t p = e / C;  // pooled pixel (n, i, j)
+        const int j = (int)(p % W2);
+        const int64_t ni = p / W2;  // n * H2 + i
+        const int64_t r0 = (2 * ni) * (2 * W2) + 2 * j;  // z pixel (n, 2i, 2j): rows of 2 W2 pixels
+        const float* b = z + r0 * C + ch;
+        out[e] = sep::pool_sel(b[0], b[C], b[2 * (int64_t)W2 * C], b[2 * (int64_t)W2 * C + C], gamma && signbit(gamma[ch]));
+    }
+}
+
 int g_sep_schedule = UNET_SEPCONV_AUTO;
 
 }  // namespace
@@ -393,7 +408,15 @@ extern "C" int unet_sepconv_fwd_supported(const unet_view* x, int n, int h, int 
 extern "C" int unet_pool_select(const float* z, int n, int h, int w, int c, const float* gamma, float* out,
                                 unet_stream_t stream) {
     UNET_CHECK_ARG(z && out && n > 0 && h > 0 && w > 0 && c > 0, "unet_pool_select: bad arguments");
-    UNET_CHECK_ARG(h % 2 == 0 && w % 2 == 0 && c % 4 == 0, "unet_pool_select: needs even h, w and c %% 4 == 0");
+    UNET_CHECK_ARG(h % 2 == 0 && w % 2 == 0, "unet_pool_select: needs even h and w");
+    if (c % 4) {  // scalar lanes (a stage of 10 filters): no alignment to ask for
+        const int64_t elems = (int64_t)n * (h / 2) * (w / 2) * c;
+        int64_t blocks = (elems + 255) / 256;
+        if (blocks > 8192) blocks = 8192;
+        pool_select_scalar_kernel<<<(unsigned)blocks, 256, 0, as_stream(stream)>>>(z, elems, h / 2, w / 2, c, gamma, out);
+        UNET_CHECK_LAUNCH("unet_pool_select");
+        return 0;
+    }
     UNET_CHECK_ARG(((uintptr_t)z | (uintptr_t)out | (uintptr_t)gamma) % 16 == 0, "unet_pool_select: 16-B alignment");
     const int64_t quads = (int64_t)n * (h / 2) * (w / 2) * (c / 4);
     int64_t blocks = (quads + 255) / 256;

@@ -26,7 +26,8 @@ import torch
 from . import _lib as L
 from . import ops
 from .ops import View
-from .params import FILTERS, VarSpec, check_input_size, count_params, flat_layout, init_weights, unet_variables
+from .params import (FILTERS, VarSpec, check_geometry, check_input_size, count_params, flat_layout, init_weights,
+                     unet_variables)
 # (block_fwd_choice and Block stay importable from here: bench.py and the tests take them from this module)
 from .plan import (FUSE_MIN_PIXELS, FUSE_MIN_TOTAL_PIXELS, RECOMPUTE_Y_COUTS, At, Block, BlockBwd, BlockFwd, Da, Dz, Knobs,
                    StepPlan, WGrad, block_fwd_choice, build_topology, plan_step)  # noqa: F401
@@ -34,7 +35,15 @@ from .plan import (FUSE_MIN_PIXELS, FUSE_MIN_TOTAL_PIXELS, RECOMPUTE_Y_COUTS, At
 BN_EPS = 1e-3       # keras BatchNormalization default epsilon
 BN_MOMENTUM = 0.99  # keras BatchNormalization default momentum
 SMOOTH = 1e-7       # K.epsilon() (utils/metrics.py:4)
-DROP_SITES = ("bneck_dropout", "dec4_dropout", "dec3_dropout", "dec2_dropout")
+
+
+def drop_sites(depth: int) -> tuple:
+    """The dropout layers of a network of `depth` levels in seed order (model/u_net.py:77-78, :98-99):
+    the bottleneck's, then the concat's of every decoder stage but the last, deepest first."""
+    return ("bneck_dropout",) + tuple(f"dec{s}_dropout" for s in range(depth, 1, -1))
+
+
+DROP_SITES = drop_sites(len(FILTERS))  # the default network's
 
 
 def _mix64(*vals: int) -> int:
@@ -90,9 +99,14 @@ class UNetEngine:
 
     def __init__(self, input_size: Sequence[int], num_classes: int = 1, dropout_rate: float = 0.2,
                  use_batch_norm: bool = True, filters: Sequence[int] = FILTERS, device=None, seed: int = 2301):
-        self.h, self.w, self.c = check_input_size(input_size, len(filters))
         if num_classes < 1:
             raise ValueError("num_classes must be >= 1")
+        filters = check_geometry(filters, num_classes)
+        self.h, self.w, self.c = check_input_size(input_size, len(filters))
+        # the network as the schedule walks it (plan.Topology; it refuses a depth whose split-precision
+        # segments do not fit one refresh launch); the routes of a step are resolved from it once per
+        # (batch, training, knobs) and cached (_plan)
+        self.topo = t = build_topology(self.h, self.w, self.c, filters, int(num_classes), bool(use_batch_norm))
         if not 0.0 <= dropout_rate < 1.0:
             raise ValueError("dropout_rate must be in [0, 1)")
         if not torch.cuda.is_available():
@@ -101,7 +115,8 @@ class UNetEngine:
         self.num_classes = int(num_classes)
         self.dropout_rate = float(dropout_rate)
         self.use_bn = bool(use_batch_norm)
-        self.filters = tuple(int(f) for f in filters)
+        self.filters = filters
+        self.drop_sites = drop_sites(len(filters))
         self.device = torch.device(device if device is not None else "cuda")
         self.seed = int(seed)
         self.specs: List[VarSpec] = unet_variables(self.c, self.num_classes, self.use_bn, self.filters)
@@ -123,9 +138,6 @@ class UNetEngine:
                 self.vars[s.name] = self.stats[o:o + s.size].view(s.shape)
         self.params_version = 0  # bumped whenever the trainable weights are replaced (set_weights / train_step)
         self.set_weights_dict(init_weights(self.specs, self.seed))
-        # the network as the schedule walks it (plan.Topology); the routes of a step are resolved
-        # from it once per (batch, training, knobs) and cached (_plan)
-        self.topo = t = build_topology(self.h, self.w, self.c, self.filters, self.num_classes, self.use_bn)
         self.cpad, self.enc, self.bneck, self.dec, self.blocks = t.cpad, t.enc, t.bneck, t.dec, t.blocks
         self._plans: Dict[tuple, StepPlan] = {}
         self._build_x3()
@@ -411,8 +423,8 @@ class UNetEngine:
         """Dropout seeds of a step, per site; data-parallel ranks salt them with their rank so the
         replicas draw independent masks (rank_salt 0 = the single-process stream)."""
         if self.rank_salt:
-            return {s: _mix64(self.seed, step, i + 1, self.rank_salt) for i, s in enumerate(DROP_SITES)}
-        return {s: _mix64(self.seed, step, i + 1) for i, s in enumerate(DROP_SITES)}
+            return {s: _mix64(self.seed, step, i + 1, self.rank_salt) for i, s in enumerate(self.drop_sites)}
+        return {s: _mix64(self.seed, step, i + 1) for i, s in enumerate(self.drop_sites)}
 
     def forward(self, x: torch.Tensor, training: bool = False, seeds: Optional[Dict[str, int]] = None) -> torch.Tensor:
         """Forward pass (model/u_net.py:55-112).  x: (N, H, W, C) float32 NHWC on the device.

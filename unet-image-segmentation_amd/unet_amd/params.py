@@ -44,6 +44,28 @@ def check_input_size(input_size: Sequence[int], depth: int = 4) -> Tuple[int, in
     return h, w, c
 
 
+HEAD_MAX_CIN = 256  # csrc/head_plan.h kMaxCin
+HEAD_MAX_CLASSES = 32  # csrc/head_plan.h kMaxCls
+
+
+def check_geometry(filters: Sequence[int], num_classes: int) -> Tuple[int, ...]:
+    """The filter tuples and class counts the kernels can run, checked where a model is built (no
+    device needed): at least one level of positive widths; the head reads the last decoder block
+    through 4-wide loads and keeps its kernel on chip, so filters[0] % 4 == 0 and filters[0] <= 256;
+    1 <= num_classes <= 32.  Deeper widths are free (blocks that are not multiples of 4 take the
+    scalar routes).  Returns the filters as a tuple of ints."""
+    f = tuple(int(v) for v in filters)
+    if not f or min(f) <= 0:
+        raise ValueError(f"filters must be a non-empty sequence of positive widths, got {tuple(filters)}")
+    if f[0] % 4:
+        raise ValueError(f"filters[0] = {f[0]}: the output head needs filters[0] % 4 == 0")
+    if f[0] > HEAD_MAX_CIN:
+        raise ValueError(f"filters[0] = {f[0]}: the output head takes at most {HEAD_MAX_CIN} input channels")
+    if not 1 <= int(num_classes) <= HEAD_MAX_CLASSES:
+        raise ValueError(f"num_classes = {num_classes}: the output head takes 1 to {HEAD_MAX_CLASSES} classes")
+    return f
+
+
 def unet_variables(input_channels: int = 3, num_classes: int = 1, use_batch_norm: bool = True,
                    filters: Sequence[int] = FILTERS) -> List[VarSpec]:
     """Every variable of U_NET in Keras creation order (layer order of the functional graph)."""

@@ -176,6 +176,11 @@ def build_topology(h: int, w: int, c: int, filters, num_classes: int, use_bn: bo
     off, offd, offt = (max(v, 8) for v in (off, offd, offt))
     mixed = tuple((so, r, cc, do + off, 1) for so, r, cc, do in x3d_segs) + \
         tuple((so, r, cc, do + off + offd, 0) for so, r, cc, do in x3t_segs)
+    # a step refreshes its live pkx planes and the rows GEMMs' in ONE launch: refuse here the depth
+    # whose segments cannot fit one, not at the first forward (7 levels and up with wide channels)
+    if len(x3_cand) + len(mixed) > L.SPLIT_MAX_SEGS:
+        raise ValueError(f"filters {f}: {len(x3_cand) + len(mixed)} split-precision weight segments, the "
+                         f"refresh launch takes at most {L.SPLIT_MAX_SEGS} (UNET_SPLIT_MAX_SEGS); use fewer levels")
     return Topology(h, w, c, cpad, tuple(enc), bneck, tuple(dec), blocks, x3_off, tuple(x3_cand), x3d_off,
                     tuple(x3d_segs), x3u_off, (off, offd, offt), mixed)
 
@@ -281,9 +286,13 @@ def block_fwd_choice(view, n: int, h: int, w: int, cout: int, training: bool, fu
     return True, training and not y_recompute
 
 
-def _fused_bwd(k: Knobs, b: Block, f: BlockFwd, drop: bool) -> bool:
-    """The block's backward runs as one unet_sepconv_bwd_fused pass (f: its training forward)."""
-    return k.fuse_block_bwd and k.fuse_bn_bwd and f.fused and not f.keep_y and not drop and b.cout == 64
+def _fused_bwd(k: Knobs, b: Block, f: BlockFwd, drop: bool, vf: ShapeView) -> bool:
+    """The block's backward runs as one unet_sepconv_bwd_fused pass (f: its training forward; vf: the
+    view its weight gradients read).  That kernel refuses a view with dropout (a 64-output block1 of a
+    decoder stage but the last): such a block takes the data-gradient GEMM plus
+    unet_sepconv_bwd_filter, which admits it."""
+    return (k.fuse_block_bwd and k.fuse_bn_bwd and f.fused and not f.keep_y and not drop and b.cout == 64
+            and not vf.dropped)
 
 
 def block_bwd_route(t: Topology, k: Knobs, b: Block, f: BlockFwd, n: int, h: int, w: int, vin: ShapeView, vf: ShapeView,
@@ -293,7 +302,7 @@ def block_bwd_route(t: Topology, k: Knobs, b: Block, f: BlockFwd, n: int, h: int
     has_target: that launch completes the da of the block vin reads; drop: dropout sits on this
     block's output; slabs_in / masked_in / rank1: what the producer of its da left for it."""
     y_recompute = f.fused and not f.keep_y
-    fused = _fused_bwd(k, b, f, drop)
+    fused = _fused_bwd(k, b, f, drop, vf)
     if rank1 and not fused:
         raise RuntimeError(f"{b.name}: rank-one da without the fused block backward")
     img_wg = img_all = False
@@ -385,7 +394,8 @@ def plan_step(t: Topology, n: int, training: bool, k: Knobs) -> StepPlan:
     last = t.dec[-1][4]
     S = ops.head_bwd_bnstats_slabs(bnrelu(last), n, t.h, t.w, k.num_classes) if producers else 0
     # binary head feeding the fused block backward: da = dlogit (x) kernel stays rank one
-    head = HeadBwd(S, S > 0 and k.num_classes == 1 and _fused_bwd(k, last, fwd[last.name], False))
+    head = HeadBwd(S, S > 0 and k.num_classes == 1 and
+                   _fused_bwd(k, last, fwd[last.name], False, vins[last.name]))
     if S:
         left[last.name] = (S, False, head.rank1)
     for i in reversed(range(nd)):
