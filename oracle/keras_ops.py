@@ -156,8 +156,10 @@ def maxpool2(a: np.ndarray) -> np.ndarray:
 
 def maxpool2_bwd(a: np.ndarray, dout: np.ndarray) -> np.ndarray:
     """MaxPoolGrad: each window's gradient goes to its FIRST maximum in row-major scan order
-    (TF CPU MaxPool argmax semantics; ties only occur between zeros after ReLU, whose
-    gradient the following ReLU mask removes)."""
+    (TF CPU MaxPool argmax semantics).  Ties are not only zeros after ReLU, whose gradient the
+    following ReLU mask removes: on images with flat regions exact ties at a POSITIVE value are
+    common (45 % of the enc1 windows of a posterised batch, tests/test_structured_data_host.py),
+    and there the tie-break decides which input element receives the gradient."""
     N, H, W, C = a.shape
     w4 = a.reshape(N, H // 2, 2, W // 2, 2, C).transpose(0, 1, 3, 2, 4, 5).reshape(N, H // 2, W // 2, 4, C)
     arg = w4.argmax(axis=3)  # numpy argmax returns the first maximum

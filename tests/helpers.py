@@ -288,6 +288,39 @@ def host_batch(rng, n, cfg):
     return x, y
 
 
+POSTER_COLOURS = 6
+
+
+def poster_batch(rng, n, cfg, cell=8):
+    """NumPy float32 images of a configuration as a decoder leaves them: per image a palette of
+    POSTER_COLOURS uint8 colours, entries 0 and 1 forced to black and white, and a (h/cell, w/cell) map
+    of palette indices expanded to cell x cell flat squares; divided by float32(255) as data.load_image
+    does.  Exact 0 and exact 1.0 occur, and every 2x2 pool window inside a cell sees four equal pixels."""
+    h, w, c = cfg[0]
+    assert h % cell == 0 and w % cell == 0
+    x = np.empty((n, h, w, c), np.float32)
+    for i in range(n):
+        pal = rng.integers(0, 256, (POSTER_COLOURS, c)).astype(np.uint8)
+        pal[0], pal[1] = 0, 255
+        idx = np.kron(rng.integers(0, POSTER_COLOURS, (h // cell, w // cell)), np.ones((cell, cell), np.int64))
+        x[i] = pal[idx].astype(np.float32) / np.float32(255)
+    return x
+
+
+def blob_masks(n, size, ncls):
+    """NumPy float32 masks (n, h, w, ncls) as a labelled set has them: image 0 empty (all background),
+    image 1 a centred rectangle of class 1, image 2 (and every later one) entirely the last class --
+    entirely 1 for the binary head; one-hot for more than one class."""
+    h, w = size[:2]
+    lab = np.zeros((n, h, w), np.int64)
+    if n > 1:
+        lab[1, h // 4:h - h // 4, w // 4:w - w // 4] = 1
+    lab[2:] = max(ncls - 1, 1)
+    if ncls == 1:
+        return lab[..., None].astype(np.float32)
+    return np.eye(ncls, dtype=np.float32)[lab]
+
+
 def batch(rng, n, cfg):
     """host_batch on the device."""
     import torch
@@ -450,10 +483,13 @@ def discrete_decisions_agree(engine, cache, p, use_bn):
 MAX_INPUT_DRAWS = 10  # a condition of the parity tests, not a tuning knob
 
 
-def train_step_parity(model, orc, draw, loss="dice_loss", lr=2e-3, wd=1e-4):
+def train_step_parity(model, orc, draw, loss="dice_loss", lr=2e-3, wd=1e-4, oracle32_weight_gate=False):
     """One train step of `model` against the float64 oracle `orc`, with the project's gates: loss and
     dice within 1e-5; every gradient's relative L2 error <= max(1e-3, 2 x the float32 oracle's own);
     the gradient key sets equal; post-AdamW weights and moving statistics within 1e-4 relative.
+    oracle32_weight_gate: that last gate becomes, per tensor, max(1e-4, 2 x the float32 oracle's own
+    error on it) -- the rule of the gradients -- for inputs on which float32 itself is close to 1e-4
+    (flat images: BatchNorm over a low-variance channel amplifies rounding).
 
     draw(attempt) -> (p, x, y): float64 weights already loaded into the model, and a NumPy batch; it is
     called again (at most MAX_INPUT_DRAWS times) until the ReLU / max-pool decisions of the device
@@ -487,7 +523,7 @@ def train_step_parity(model, orc, draw, loss="dice_loss", lr=2e-3, wd=1e-4):
     assert abs(res[1] - dice) < 1e-5
     # fp32 conditioning reference: the same oracle step in float32
     p32 = {k: v.astype(np.float32) for k, v in p.items()}
-    prob32, cache32, _ = orc.forward(p32, x, training=True, drop_seeds=seeds if drop > 0 else None)
+    prob32, cache32, stats32 = orc.forward(p32, x, training=True, drop_seeds=seeds if drop > 0 else None)
     _, dprob32 = orc.loss_and_dprob(y, prob32, okind)
     g32, _ = orc.backward(p32, cache32, dprob32)
     bad = {}
@@ -509,11 +545,19 @@ def train_step_parity(model, orc, draw, loss="dice_loss", lr=2e-3, wd=1e-4):
     assert set(g) == set(grads)
     stat = {s.name for s in model.engine.specs if not s.trainable}
     out["weights"] = out["stats"] = 0.0
+    new32 = dict(stats32)
+    if oracle32_weight_gate:  # the float32 oracle's own step: adamw_f32 from zero moments at t = 1
+        alpha = AdamW(learning_rate=lr, weight_decay=wd).alpha(1)
+        for k, g_ in g32.items():
+            zero = np.zeros_like(p32[k])
+            new32[k] = adamw_f32(p32[k], g_, zero, zero, lr, wd, 0.9, 0.999, 1e-7, alpha)[0]
+        out["weights_err_oracle32"] = max(rel_err(new32[k], v) for k, v in newp.items())
     for k, v in newp.items():
         e = rel_err(neww[k], v)
+        tol = max(1e-4, 2.0 * rel_err(new32[k], v)) if oracle32_weight_gate else 1e-4
         which = "stats" if k in stat else "weights"
-        out[which] = max(out[which], e / 1e-4)
-        assert e < 1e-4, k
+        out[which] = max(out[which], e / tol)
+        assert e < tol, (k, e, tol)
     return out
 
 
@@ -550,14 +594,36 @@ def geometry_draw(name, attempt, base=None):
     return (w32,) + host_batch(rng, n, cfg)
 
 
-def geometry_oracle32_agrees(name, attempt, base=None):
+# Seed base of each flat-image train-step case (draw k uses base + 1000 k), by GEOMETRY_SEEDS' rule on
+# flat_draw: the first base of 9000, 9001, ... at which the float32 oracle's decisions of draw 0 agree with
+# float64's (tests/test_structured_data_host.py pins both the rule and what the inputs contain).
+FLAT_SEEDS = {"not4": 9000, "one_level": 9000, "deep5": 9000}
+FLAT_BATCH = {"deep5": 2}  # (GEOMETRIES' own batch of 1 would hold the empty mask alone)
+
+
+def flat_draw(name, attempt, base=None):
+    """geometry_draw on structured data: the same weight recipe, x from poster_batch, y from blob_masks.
+    Without BatchNorm (deep5) every bias is zero, as in a fresh network: a black pixel's pre-activation
+    z + b is then exactly 0."""
+    from unet_amd.params import init_weights, unet_variables
+    cfg, filters, n = geometry_cfg(name)
+    n = FLAT_BATCH.get(name, n)
+    size, ncls, bn = cfg[0], cfg[1], cfg[2]
+    rng = np.random.default_rng((FLAT_SEEDS[name] if base is None else base) + 1000 * attempt)
+    w32 = randomised_stats(init_weights(unet_variables(size[2], ncls, bn, filters), GEOMETRY_ENGINE_SEED), rng)
+    if not bn:
+        w32 = {k: np.zeros_like(v) if k.endswith("/bias") else v for k, v in w32.items()}
+    return w32, poster_batch(rng, n, cfg), blob_masks(n, size, ncls)
+
+
+def geometry_oracle32_agrees(name, attempt, base=None, draw=geometry_draw):
     """True if the float32 oracle's training forward of draw `attempt` makes the ReLU / max-pool
     decisions of the float64 one (step attempt + 1 of the engine's dropout stream)."""
     from oracle.unet_ref import UNetOracle
     from unet_amd.engine import _mix64, drop_sites
     cfg, filters, _ = geometry_cfg(name)
     _, ncls, bn, drop, _ = cfg
-    w32, x, _ = geometry_draw(name, attempt, base)
+    w32, x, _ = draw(name, attempt, base)
     seeds = {s: _mix64(GEOMETRY_ENGINE_SEED, attempt + 1, i + 1) for i, s in enumerate(drop_sites(len(filters)))}
     orc = UNetOracle(ncls, drop, bn, filters)
     pre = []

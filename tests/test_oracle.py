@@ -111,6 +111,24 @@ def test_maxpool_first_max_routing():
     assert g[0, 0, 1, 0] == 1 and g[0, 1, 0, 0] == 0 and g[0, 1, 1, 1] == 1
 
 
+def test_maxpool_positive_ties_route_like_torch():
+    """Positive ties (flat image regions produce them): a three-way tie whose first element is lower, all
+    four equal, and every pair / triple pattern over a random batch, against torch-CPU float64 autograd of
+    max_pool2d, which also sends a window's gradient to its first maximum in row-major order."""
+    a = np.full((1, 2, 2, 2), 2.5)
+    a[0, 0, 0, 0] = 1.0  # channel 0: (0,1), (1,0), (1,1) tie at 2.5 above (0,0); channel 1: all four equal
+    dout = np.array([3.0, 5.0]).reshape(1, 1, 1, 2)
+    g = K.maxpool2_bwd(a, dout)
+    assert g[0, :, :, 0].tolist() == [[0, 3], [0, 0]] and g[0, :, :, 1].tolist() == [[5, 0], [0, 0]]
+    rng = np.random.default_rng(3)
+    b = rng.integers(1, 3, (2, 8, 6, 5)).astype(np.float64)  # two positive levels: ties in nearly every window
+    db = rng.standard_normal((2, 4, 3, 5))
+    for arr, d in ((a, dout), (b, db)):
+        t = torch.tensor(arr).permute(0, 3, 1, 2).clone().requires_grad_(True)
+        (F.max_pool2d(t, 2) * torch.tensor(d).permute(0, 3, 1, 2)).sum().backward()
+        assert np.array_equal(t.grad.permute(0, 2, 3, 1).numpy(), K.maxpool2_bwd(arr, d))
+
+
 def test_dropout_mask_statistics():
     m = K.dropout_mult(12345, (4, 64, 64, 32), 0.2, np.float64)
     keep = (m > 0).mean()
