@@ -105,7 +105,7 @@ int main() {
                 CHECK(b.grid >= 1 && b.grid <= cdiv(M, 256));
                 // The workspace holds what the route's layout touches.  The weight-gradient scratch is
                 // wgrad_workspace's formula restated over wgrad_plan (gemm_wgrad.hip cannot be built
-                // without device code); the column sum's plan lives beside its kernel in bn.hip, so the
+                // without device code); the column sum's plan is bn_plan.h's, pinned by bn_plan_check.cpp, so the
                 // bound is checked for a column-sum need below and above the weight gradient's.
                 const WgradPlan w = wgrad_plan(M, c0, ncls);
                 const size_t wg = align_up((size_t)w.S * c0 * ncls * sizeof(float), 256);

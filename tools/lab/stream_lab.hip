@@ -1,6 +1,6 @@
-// Streaming-kernel lab: BN-backward statistics reduce (product kernel from bn.hip) vs a plain
+// Streaming-kernel lab: BN-backward statistics reduce (product kernel from bn_bwd.hip) vs a plain
 // two-tensor read of the same bytes, at the U-Net's level-0..2 shapes.
-#include "bn.hip"
+#include "bn_bwd.hip"
 #include <vector>
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP %s line %d\n", hipGetErrorString(e), __LINE__); exit(1);} } while (0)
 using namespace unet;

@@ -34,6 +34,13 @@ inline hipStream_t as_stream(unet_stream_t s) { return reinterpret_cast<hipStrea
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// blocks of 256 threads for a grid-stride loop over `work` items
+inline int grid_for(int64_t work) {
+    int64_t g = cdiv(work, 256);
+    if (g > 65536) g = 65536;
+    if (g < 1) g = 1;
+    return (int)g;
+}
 
 // Tuning knobs read from the environment exist only in the lab build (`make lab` ->
 // libunet_hip_lab.so, -DUNET_LAB_BUILD, loaded by the tools through UNET_HIP_LIB).  The product
@@ -130,7 +137,7 @@ __device__ __forceinline__ float bnrelu(float x, float sc, float sh) { return re
 __device__ __forceinline__ float4 bnrelu4(float4 x, float4 sc, float4 sh) { return relu4(fma4(x, sc, sh)); }
 // The BatchNorm + ReLU backward operand of four channels: g = da (dropout already applied where the
 // block has one) masked by the ReLU, then dz = sc * (g - p - (z - mu) * q) with the per-channel
-// (mu, p, q) of bn.hip's finish.  The one definition every kernel that forms dz on the fly uses.
+// (mu, p, q) of bn_bwd.hip's finish.  The one definition every kernel that forms dz on the fly uses.
 // In place (g in, dz out).  The statements live in a macro so that gemm_rows_vec, whose generated
 // code changes when they arrive through an inlined function, can take them as text; every other
 // kernel calls bn_bwd_dz4.
@@ -211,5 +218,9 @@ int reduce_slabs(float* part, int S, int64_t L, float* out, int64_t row, int64_t
 // partial arrays: pointwise + depthwise kernel, head kernel + bias) in ONE launch; outputs flat.
 int reduce_slabs_pair(const float* part_a, int64_t la, float* out_a, const float* part_b, int64_t lb, float* out_b,
                       int S, hipStream_t stream);
+// out[c] = sum over rows of x[rows][cols] (a bias gradient), fixed order: per-chunk sums into ws
+// (colsum_workspace bytes; bn_plan.h colsum_plan), then reduce_slabs.
+int colsum(const float* x, int64_t rows, int cols, float* out, void* ws, size_t ws_bytes, hipStream_t st);
+size_t colsum_workspace(int64_t rows, int cols);
 
 }  // namespace unet

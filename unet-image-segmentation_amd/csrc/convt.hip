@@ -2,7 +2,6 @@
 // GEMM [M, Cin] x [Cin, 4 Cout] with a pixel-shuffle + bias epilogue, the data gradient a rows
 // GEMM with a pixel-unshuffle A operand, and the kernel gradient a weight-gradient GEMM (gemm.h).
 #include "gemm.h"
-#include "head.h"  // colsum, colsum_workspace
 
 using namespace unet;
 

@@ -4,7 +4,7 @@
 // pinned by tests/dw_plan_check.cpp.  A change of a route, a tile shape or a block count is a change here and
 // in that file's pinned rows.
 #pragma once
-#include "common.h"  // cdiv, align_up, lab_knob
+#include "common.h"  // cdiv, align_up, grid_for, lab_knob
 
 namespace unet {
 namespace dw {
@@ -26,13 +26,6 @@ inline int qt_for(int C) {
     if (C % 64 == 0) return 16;  // (8 quads x 32 columns measured -0.6 % img/s, round 2)
     const int q = C / 4;
     return (q == 1 || q == 2 || q == 4 || q == 8) ? q : 0;
-}
-
-inline int grid_for(int64_t work) {
-    int64_t g = cdiv(work, kThreads);
-    if (g > 65536) g = 65536;
-    if (g < 1) g = 1;
-    return (int)g;
 }
 
 enum { DW_FLAT_SCALAR, DW_FLAT_VEC, DW_TILED };

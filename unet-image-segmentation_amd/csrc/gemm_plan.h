@@ -9,7 +9,7 @@ constexpr int BK = 16;  // k (rows GEMM) or m (weight gradient) per stage of the
 
 // A_BNBWD: A = dz of a BatchNorm + ReLU (+ dropout) output, formed on load from the incoming
 // gradient da (a.src0) and the raw pre-BN z: g = da * drop * [z*sc+sh > 0],
-// dz = sc * (g - p - (z - mu) * q) with per-channel (mu, p, q) = coef[0..3C) (see bn.hip).
+// dz = sc * (g - p - (z - mu) * q) with per-channel (mu, p, q) = coef[0..3C) (see bn_bwd.hip).
 enum { A_PLAIN = 0, A_BNRELU = 1, A_UNSHUFFLE = 2, A_BNBWD = 3 };
 // E_BNPART: E_STORE, and the stored C is the complete da of a BatchNorm + ReLU block whose raw
 // z is g.z (same [M][N] layout): the tile also emits that block's BN-backward partial sums

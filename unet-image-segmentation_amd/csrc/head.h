@@ -15,12 +15,10 @@
 
 namespace unet {
 
-// gemm_wgrad.hip, bn.hip: the dlogit routes' weight gradient and bias gradient (also convt.hip's)
+// gemm_wgrad.hip: the dlogit routes' weight gradient (their bias gradient is common.h's colsum)
 int head_wgrad(const unet_view* x, int64_t M, const float* dlogit, int ncls, float* dkernel, void* ws,
                size_t ws_bytes, hipStream_t st);
 size_t head_wgrad_workspace(int64_t M, int cin, int ncls);
-int colsum(const float* x, int64_t rows, int cols, float* out, void* ws, size_t ws_bytes, hipStream_t st);
-size_t colsum_workspace(int64_t rows, int cols);
 
 // Channels [c, c + 4) of row m for the two general forward kernels.  al = false: src0 is only 4-byte
 // aligned (the caller's predicate sent it here), so the row is read element by element.

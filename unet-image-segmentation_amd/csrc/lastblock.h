@@ -14,21 +14,12 @@
 // Cost note (measured, r1zc/r1zd): the vmcnt(0) wait also covers the block's other stores, so in
 // a streaming kernel with thousands of blocks every block lives one store round trip longer; the
 // 256x256 depthwise data gradient lost 46 us per launch that way.  Use it in kernels whose blocks
-// store little (the statistics reductions of bn.hip), not in the producers themselves.
+// store little (the statistics reductions of bn_fwd.hip and bn_bwd.hip, whose buffers bn_plan.h lays
+// out), not in the producers themselves.
 #pragma once
 #include "common.h"
 
 namespace unet {
-
-constexpr int kGroupSlabs = 64;  // slabs per first-pass block of the BN-backward statistics
-
-// byte layout of a producer-side BN-backward partials buffer of S slabs x 2C floats:
-// slabs | double chunk rows (one per 64 slabs) | cdiv(C, 64) arrival counters (u32)
-inline size_t bnpart_scratch_off(int S, int C) { return align_up((size_t)S * 2 * C * sizeof(float), 256); }
-inline size_t bnpart_counter_off(int S, int C) {
-    return bnpart_scratch_off(S, C) + align_up((size_t)cdiv(S, kGroupSlabs) * 2 * C * sizeof(double), 256);
-}
-inline size_t bnpart_bytes(int S, int C) { return bnpart_counter_off(S, C) + (size_t)cdiv(C, 64) * sizeof(unsigned); }
 
 __device__ __forceinline__ void st_agent(double* p, double v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

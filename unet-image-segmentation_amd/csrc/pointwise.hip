@@ -3,15 +3,7 @@
 // GEMMs (gemm.h); the streaming dz pass of the widest data gradients lives here too.
 #include "gemm.h"
 
-namespace unet {
-size_t bn_partials_bytes(int64_t m, int c);
-}
 using namespace unet;
-
-extern "C" size_t unet_bn_partials_size(int64_t m, int c) {
-    if (m <= 0 || c <= 0) return 0;
-    return bn_partials_bytes(m, c);  // partials + the finalize's chunk scratch (bn.hip)
-}
 
 namespace {
 int pw_fwd(const float* y, int64_t m, int cin, int cout, const float* pw_kernel, const unsigned short* pw_kernel_x3,

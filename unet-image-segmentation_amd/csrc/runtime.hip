@@ -1,7 +1,8 @@
-// Error reporting, view validation and the deterministic slab reduction shared by
-// every op of libunet_hip.so.
+// Error reporting, view validation, the deterministic slab reduction and the column sum shared by
+// the ops of libunet_hip.so.
 #include <stdarg.h>
 
+#include "bn_plan.h"
 #include "view.h"
 
 namespace unet {
@@ -238,6 +239,38 @@ __global__ __launch_bounds__(512) void reduce_pair_kernel(SlabArr a, SlabArr b, 
             if (l + k < L) out[l + k] = (float)red[k][q];
     }
 }
+
+// colsum's first pass: part[chunk][c] = sum of x[m][c] over the chunk's rows (bn_plan.h RedPlan geometry)
+template <bool VEC>
+__global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ x, int64_t rows, int C, int CT,
+                                                     int64_t rpc, float* __restrict__ part) {
+    const int CQ = VEC ? C / 4 : C;
+    const int PL = 256 / CT;
+    const int tid = threadIdx.x, cl = tid % CT, pl = tid / CT;
+    const int cq = blockIdx.x * CT + cl;
+    const int64_t r0 = (int64_t)blockIdx.y * rpc;
+    const int64_t r1 = r0 + rpc < rows ? r0 + rpc : rows;
+    __shared__ float4 red[256];
+    float4 s = f4(0.f);
+    if (pl < PL && cq < CQ) {
+        if constexpr (VEC) {
+            for (int64_t m = r0 + pl; m < r1; m += PL) s = add4(s, ld4(x + m * C + cq * 4));
+        } else {
+            for (int64_t m = r0 + pl; m < r1; m += PL) s.x += x[m * C + cq];
+        }
+    }
+    red[tid] = s;
+    __syncthreads();
+    if (pl == 0 && cq < CQ) {
+        float4 a = red[cl];
+        for (int q = 1; q < PL; ++q) a = add4(a, red[q * CT + cl]);
+        float* out = part + (int64_t)blockIdx.y * C;
+        if constexpr (VEC)
+            st4(out + cq * 4, a);
+        else
+            out[cq] = a.x;
+    }
+}
 }  // namespace
 
 int reduce_slabs_pair(const float* part_a, int64_t la, float* out_a, const float* part_b, int64_t lb, float* out_b,
@@ -315,6 +348,23 @@ int reduce_slabs(float* part, int S, int64_t L, float* out, int64_t row, int64_t
     }
     UNET_CHECK_LAUNCH("reduce_slabs");
     return 0;
+}
+
+size_t colsum_workspace(int64_t rows, int cols) { return bn::colsum_plan(rows, cols).bytes; }
+
+int colsum(const float* x, int64_t rows, int cols, float* out, void* ws, size_t ws_bytes, hipStream_t st) {
+    const bool vec = cols % 4 == 0 && (uintptr_t)x % 16 == 0;  // float4 loads of x
+    const bn::ColsumPlan c = bn::colsum_plan(rows, cols, vec);
+    const bn::RedPlan& p = c.red;
+    UNET_CHECK_ARG(ws && ws_bytes >= c.need, "colsum: workspace %zu < %zu", ws_bytes, c.need);
+    float* part = static_cast<float*>(ws);
+    dim3 grid(p.ctiles, (unsigned)p.chunks);
+    if (vec)
+        colsum_kernel<true><<<grid, 256, 0, st>>>(x, rows, cols, p.CT, p.rpc, part);
+    else
+        colsum_kernel<false><<<grid, 256, 0, st>>>(x, rows, cols, p.CT, p.rpc, part);
+    UNET_CHECK_LAUNCH("colsum");
+    return reduce_slabs(part, (int)p.chunks, cols, out, cols, cols, st);
 }
 
 }  // namespace unet
