@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define UNET_ABI_VERSION 17
+#define UNET_ABI_VERSION 18
 
 typedef void* unet_stream_t; /* hipStream_t */
 
@@ -758,6 +758,39 @@ int unet_mask_largest_contour(const unsigned char* mask, int h, int w, unet_cont
  * not 4-byte aligned.                                                                            */
 int unet_batch_gather_u8(const unsigned char* src, int n, int h, int w, int c, const int* slots,
                          int b, float* dst, unet_stream_t stream);
+
+/* ----- Random affine augmentation, warped on the device (ABI 18) ------------------------------
+ * The batch gather with Keras' ImageDataGenerator rotation / shift / shear / zoom in it
+ * (apply_affine_transform; unet_amd/augment.py draws the parameters and builds the records).
+ *
+ * src: as above.  slots: b device int32 sample indices, clamped to [0, n-1] on the device; there is
+ * no flip encoding, the flip is in the record.  xforms: (b, 6) device fp32, the transform record of
+ * each batch position, [m00 m01 o0 m10 m11 o1]: output pixel (r, q) samples source row
+ * m00 r + m01 q + o0 and source column m10 r + m11 q + o1.  order: 0 nearest, 1 bilinear.
+ * fill_constant: 0 replicates the border (Keras fill_mode "nearest"), else pixels whose source point
+ * lies outside the image take cval (in 0..255 units).  dst: (b, h, w, c) fp32.
+ *
+ * The arithmetic is fp32, one rounding per operation, no contraction, in this order:
+ *     sy = (m00 * (float)r + m01 * (float)q) + o0;   sx = (m10 * (float)r + m11 * (float)q) + o1
+ *     outside = sy < 0 || sy > h-1 || sx < 0 || sx > w-1
+ *     sy = clamp(sy, 0, h-1);   sx = clamp(sx, 0, w-1)
+ *     order 1:  y0 = min((int)floorf(sy), max(h-2, 0)), y1 = min(y0 + 1, h-1), fy = sy - (float)y0,
+ *               likewise x0, x1, fx; per channel, the four bytes converted to float,
+ *               top = p00 + fx * (p01 - p00), bot = p10 + fx * (p11 - p10), v = top + fy * (bot - top)
+ *     order 0:  v = p[min((int)floorf(sy + 0.5f), h-1)][min((int)floorf(sx + 0.5f), w-1)]
+ *     fill_constant: v = outside ? cval : v
+ *     dst = v / 255.0f (the IEEE divide)
+ * bitwise augment.affine_u8_reference.  The identity record reproduces unet_batch_gather_u8 of the
+ * plain sample, the record [1 0 0 0 -1 w-1] that of the mirrored one.  A non-finite record reads
+ * inside the sample like any other: a NaN coordinate is not outside and clamps to 0 (fmaxf / fminf
+ * return the other operand), an infinite one is outside and clamps to the border.  Every element of dst is written and nothing else.
+ * One launch.  w % 4 == 0 with dst 16-byte aligned takes the 16-byte-store kernel (a thread owns 4
+ * consecutive pixels of a row); any other w or alignment a one-float-per-thread one with the same
+ * result.  Refused with an error message and no launch: a null pointer, n, h, w or b < 1, c outside
+ * {1, 3}, order outside {0, 1}, h * w * c > 2^31 - 1, dst, slots or xforms not 4-byte aligned.     */
+int unet_batch_affine_u8(const unsigned char* src, int n, int h, int w, int c, const int* slots,
+                         const float* xforms, int b, int order, int fill_constant, float cval,
+                         float* dst, unet_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,10 @@ Same flags and defaults (reference scripts/train.py:71-117): --epochs 30 --batch
 synchronised horizontal flips for training, same callbacks (ModelCheckpoint on
 val_mean_io_u, EarlyStopping patience 10, ReduceLROnPlateau factor 0.2 patience 3).
 Extras: --synthetic N (no dataset needed), --device_loader (the decoded training set stays on the
-GPU as uint8, batches are built there; same batches), data-parallel via torchrun env (one process per
+GPU as uint8, batches are built there; same batches), --rotation-range / --width-shift-range /
+--height-shift-range / --shear-range / --zoom-range / --fill-mode / --cval / --mask-order (Keras'
+ImageDataGenerator affine augmentation of the training input, the step the reference's train.py:180
+suggests; off by default, warped on the GPU with --device_loader), data-parallel via torchrun env (one process per
 GPU, each rank takes its shard of every global batch).  The model file is the engine's
 neutral .npz weight file (Keras names and layouts), whatever the extension.
 """
@@ -62,7 +65,31 @@ def parse_args(argv=None) -> argparse.Namespace:
     parser.add_argument("--device_loader", action="store_true",
                         help="Keep the decoded samples on the GPU as uint8 and build every batch there "
                              "(same batches; no effect with --synthetic).")
+    aug = parser.add_argument_group("augmentation of the training input (Keras ImageDataGenerator names; all off "
+                                    "by default, no effect with --synthetic, never applied to validation)")
+    aug.add_argument("--rotation-range", type=float, default=0.0, help="Degrees; rotation drawn from [-r, r].")
+    aug.add_argument("--width-shift-range", type=float, default=0.0, help="Fraction of the width in [0, 1).")
+    aug.add_argument("--height-shift-range", type=float, default=0.0, help="Fraction of the height in [0, 1).")
+    aug.add_argument("--shear-range", type=float, default=0.0, help="Degrees; shear drawn from [-s, s].")
+    aug.add_argument("--zoom-range", type=float, nargs="+", default=[0.0], metavar="Z",
+                     help="One number z for [1 - z, 1 + z], or two: low high.")
+    aug.add_argument("--fill-mode", choices=("nearest", "constant"), default="nearest",
+                     help="What a pixel sampled outside the image takes: the nearest border pixel, or --cval.")
+    aug.add_argument("--cval", type=float, default=0.0, help="The constant of --fill-mode constant, in 0..255.")
+    aug.add_argument("--mask-order", type=int, choices=(0, 1), default=1,
+                     help="Interpolation of the masks: 1 bilinear (what Keras' paired generators do), 0 nearest "
+                          "(keeps a mask on its own grey levels).")
     return parser.parse_args(argv)
+
+
+def augment_from_args(args):
+    """The Augment of the training loader, or None when every range is off."""
+    from unet_amd.augment import Augment
+    zoom = args.zoom_range[0] if len(args.zoom_range) == 1 else tuple(args.zoom_range)
+    a = Augment(rotation_range=args.rotation_range, width_shift_range=args.width_shift_range,
+                height_shift_range=args.height_shift_range, shear_range=args.shear_range, zoom_range=zoom,
+                fill_mode=args.fill_mode, cval=args.cval, mask_order=args.mask_order)
+    return a if a.active else None
 
 
 def count_samples(train, val, root="."):
@@ -153,7 +180,7 @@ def main(argv=None):
                 loader = PairLoader
             train = loader(os.path.join(root, TRAIN_FRAMES_DIR), os.path.join(root, TRAIN_MASKS_DIR),
                            TARGET_SIZE, args.batch_size, SEED, shuffle=True, horizontal_flip=True,
-                           rank=rank, world=world)
+                           rank=rank, world=world, augment=augment_from_args(args))
             val = loader(os.path.join(root, VAL_FRAMES_DIR), os.path.join(root, VAL_MASKS_DIR), TARGET_SIZE,
                          args.batch_size, SEED, shuffle=False, horizontal_flip=False, rank=rank, world=world)
         say("Data Generators created successfully.")

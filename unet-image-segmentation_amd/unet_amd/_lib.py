@@ -12,7 +12,7 @@ from pathlib import Path
 
 LIB_NAME = "libunet_hip.so"
 LIB_PATH = Path(os.environ.get("UNET_HIP_LIB", Path(__file__).with_name(LIB_NAME)))
-ABI_VERSION = 17
+ABI_VERSION = 18
 SPLIT_MAX_SEGS = 64  # UNET_SPLIT_MAX_SEGS
 
 VIEW_PLAIN, VIEW_BNRELU, VIEW_POOL_BNRELU, VIEW_CONCAT = 0, 1, 2, 3
@@ -179,6 +179,7 @@ SIGNATURES = {
     "unet_mask_largest_contour_workspace": (c_size_t, [c_int, c_int]),
     "unet_mask_largest_contour": (c_int, [P, c_int, c_int, P, P, c_size_t, P]),
     "unet_batch_gather_u8": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, P, P]),
+    "unet_batch_affine_u8": (c_int, [P, c_int, c_int, c_int, c_int, P, P, c_int, c_int, c_int, c_float, P, P]),
 }
 
 _lib = None

@@ -25,6 +25,7 @@ from typing import Iterator, Tuple
 
 import numpy as np
 
+from .augment import affine_u8_reference
 from .dp import shard_bounds
 
 
@@ -97,9 +98,11 @@ class PairLoader:
     not shrink with the rank count."""
 
     def __init__(self, frames_dir, masks_dir, size, batch_size, seed, shuffle=True, horizontal_flip=False, rank=0,
-                 world=1, workers=16, cache_bytes=None):
+                 world=1, workers=16, cache_bytes=None, augment=None):
         if batch_size < world:
             raise ValueError(f"batch size {batch_size} < {world} data-parallel ranks: every rank needs a sample")
+        # an augment.Augment with a non-zero range; None or all ranges 0: today's code path and RNG stream
+        self.augment = augment if augment is not None and augment.active else None
         self.frames = [os.path.join(frames_dir, f) for f in _list(frames_dir)]
         self.masks = [os.path.join(masks_dir, f) for f in _list(masks_dir)]
         if len(self.frames) != len(self.masks):
@@ -127,10 +130,16 @@ class PairLoader:
             rng = np.random.default_rng(self.seed + epoch)
             order = rng.permutation(self.samples) if self.shuffle else np.arange(self.samples)
             flips = rng.random(self.samples) < 0.5 if self.flip else np.zeros(self.samples, bool)
+            # one further draw, after order and flips and on every rank alike: the epoch's affine parameters
+            table = self.augment.draw(rng, self.samples) if self.augment else None
             for b0, b1 in global_batches(self.samples, self.batch_size, self.world):
                 idx = order[b0:b1]
                 lo, hi = shard_bounds(len(idx), self.world, self.rank)
-                yield Shard(*self.load(idx[lo:hi], flips), global_size=len(idx))
+                if table is None:
+                    xy = self.load(idx[lo:hi], flips)
+                else:
+                    xy = self.load(idx[lo:hi], flips, self.augment.records(table, idx[lo:hi], flips, self.size))
+                yield Shard(*xy, global_size=len(idx))
             epoch += 1
 
     def _sample_u8(self, i, keep=True):
@@ -146,24 +155,30 @@ class PairLoader:
                     self._cached_bytes += nb
         return xy
 
-    def _sample(self, i, flip):
+    def _sample(self, i, flip, record=None):
         xy = self._sample_u8(i)
+        if record is not None:  # the warp kernel's restatement; the flip is in the record
+            a = self.augment
+            return tuple(affine_u8_reference(u[None], [0], record[None], o, a.fill_constant, a.cval)[0]
+                         for u, o in ((xy[0], a.frame_order), (xy[1], a.mask_order)))
         x = xy[0].astype(np.float32) / 255.0  # rescale=1/255 (reference scripts/train.py:170-178)
         y = xy[1].astype(np.float32) / 255.0
         if flip:
             x, y = x[:, ::-1], y[:, ::-1]
         return x, y
 
-    def load(self, idx, flips):
+    def load(self, idx, flips, records=None):
         """Decode the samples idx (PIL releases the GIL while decoding / resizing, so a small
-        thread pool decodes a batch in parallel); returns contiguous (x, y) batches."""
+        thread pool decodes a batch in parallel); returns contiguous (x, y) batches.  records: the
+        batch's transform records (augment.Augment.records), one per entry of idx."""
+        jobs = [(int(i), bool(flips[i]), None if records is None else records[k]) for k, i in enumerate(idx)]
         if self.workers > 1 and len(idx) > 1:
             if self._pool is None:
                 from concurrent.futures import ThreadPoolExecutor
                 self._pool = ThreadPoolExecutor(self.workers, thread_name_prefix="unet-decode")
-            pairs = list(self._pool.map(lambda i: self._sample(int(i), bool(flips[i])), idx))
+            pairs = list(self._pool.map(lambda j: self._sample(*j), jobs))
         else:
-            pairs = [self._sample(int(i), bool(flips[i])) for i in idx]
+            pairs = [self._sample(*j) for j in jobs]
         return (np.ascontiguousarray(np.stack([p[0] for p in pairs])),
                 np.ascontiguousarray(np.stack([p[1] for p in pairs])))
 

@@ -22,6 +22,7 @@ from typing import List, NamedTuple, Tuple
 
 import numpy as np
 
+from .augment import affine_u8_reference
 from .data import PairLoader, gather_u8_reference
 from .dp import shard_bounds
 
@@ -101,27 +102,39 @@ def upload_runs(uploads):
 
 
 class _HostStore:
-    """The device's part in NumPy: two uint8 buffers and gather_u8_reference."""
+    """The device's part in NumPy: two uint8 buffers and gather_u8_reference (affine_u8_reference
+    for a batch that comes with transform records)."""
 
-    def __init__(self, slots, size):
+    def __init__(self, slots, size, augment=None):
         h, w = size
+        self.augment = augment
         self.frames = np.zeros((max(slots, 1), h, w, 3), np.uint8)
         self.masks = np.zeros((max(slots, 1), h, w, 1), np.uint8)
         self.uploaded_bytes = 0
 
-    def batch(self, plan: BatchPlan, pairs):
+    def batch(self, plan: BatchPlan, pairs, records=None):
         for (_, slot), (f, m) in zip(plan.uploads, pairs):
             self.frames[slot], self.masks[slot] = f, m
             self.uploaded_bytes += f.nbytes + m.nbytes
+        if records is not None:
+            a = self.augment
+            return (affine_u8_reference(self.frames, plan.entries, records, a.frame_order, a.fill_constant, a.cval),
+                    affine_u8_reference(self.masks, plan.entries, records, a.mask_order, a.fill_constant, a.cval), None)
         return gather_u8_reference(self.frames, plan.entries), gather_u8_reference(self.masks, plan.entries), None
 
 
 class _StagingArea:
-    def __init__(self, torch, pairs, fbytes, mbytes):
-        self.buf = torch.empty(pairs * (fbytes + mbytes) + 4 * pairs, dtype=torch.uint8, pin_memory=True)
+    """One pinned buffer: the batch's new sample bytes and its table.  The table is `pairs` int32
+    slot entries; for an augmented batch of b positions it is b entries followed at once by b
+    transform records of 6 fp32 (room for 7 words per pair), so entries and records go up in one copy."""
+
+    def __init__(self, torch, pairs, fbytes, mbytes, record_words=0):
+        words = pairs * (1 + record_words)
+        self.buf = torch.empty(pairs * (fbytes + mbytes) + 4 * words, dtype=torch.uint8, pin_memory=True)
         self.frames = self.buf[:pairs * fbytes].view(pairs, fbytes)
         self.masks = self.buf[pairs * fbytes:pairs * (fbytes + mbytes)].view(pairs, mbytes)
-        self.entries = self.buf[pairs * (fbytes + mbytes):].view(torch.int32)
+        self.table = self.buf[pairs * (fbytes + mbytes):].view(torch.int32)
+        self.entries = self.table[:pairs]
         self.event = None  # recorded after the last copy that reads this area was issued
 
 
@@ -130,8 +143,9 @@ class _DeviceStore:
     rewritten only after the event behind its last copies has completed (a ring of STAGING_RING
     areas, so the wait is for a batch issued that many batches ago)."""
 
-    def __init__(self, slots, size, pairs, device):
+    def __init__(self, slots, size, pairs, device, augment=None):
         import torch
+        self.augment = augment
         self.torch = torch
         self.device = torch.device(device)
         h, w = size
@@ -146,11 +160,12 @@ class _DeviceStore:
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
         self.frames.record_stream(self.stream)
         self.masks.record_stream(self.stream)
-        self.ring = [_StagingArea(torch, pairs, self.fbytes, self.mbytes) for _ in range(STAGING_RING)]
+        self.ring = [_StagingArea(torch, pairs, self.fbytes, self.mbytes, 6 if augment else 0)
+                     for _ in range(STAGING_RING)]
         self.turn = 0
         self.uploaded_bytes = 0
 
-    def batch(self, plan: BatchPlan, pairs):
+    def batch(self, plan: BatchPlan, pairs, records=None):
         from . import ops
         torch = self.torch
         area = self.ring[self.turn]
@@ -163,18 +178,27 @@ class _DeviceStore:
             fv[p] = f.reshape(-1)
             mv[p] = m.reshape(-1)
         area.entries.numpy()[:b] = plan.entries
+        if records is not None:
+            area.table[b:7 * b].view(torch.float32).numpy()[:] = records.reshape(-1)
         fdev = self.frames.view(self.frames.shape[0], self.fbytes)
         mdev = self.masks.view(self.masks.shape[0], self.mbytes)
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
             for p, slot, cnt in upload_runs(plan.uploads):
                 fdev[slot:slot + cnt].copy_(area.frames[p:p + cnt], non_blocking=True)
                 mdev[slot:slot + cnt].copy_(area.masks[p:p + cnt], non_blocking=True)
-            entries = torch.empty(b, dtype=torch.int32, device=self.device)
-            entries.copy_(area.entries[:b], non_blocking=True)
+            words = b if records is None else 7 * b
+            table = torch.empty(words, dtype=torch.int32, device=self.device)
+            table.copy_(area.table[:words], non_blocking=True)
+            entries = table[:b]
             x = torch.empty((b, h, w, 3), dtype=torch.float32, device=self.device)
             y = torch.empty((b, h, w, 1), dtype=torch.float32, device=self.device)
-            ops.batch_gather_u8(self.frames, entries, x)
-            ops.batch_gather_u8(self.masks, entries, y)
+            if records is None:
+                ops.batch_gather_u8(self.frames, entries, x)
+                ops.batch_gather_u8(self.masks, entries, y)
+            else:
+                a, xf = self.augment, table[b:].view(torch.float32).view(b, 6)
+                ops.batch_affine_u8(self.frames, entries, xf, x, a.frame_order, a.fill_constant, a.cval)
+                ops.batch_affine_u8(self.masks, entries, xf, y, a.mask_order, a.fill_constant, a.cval)
             if area.event is None:
                 area.event = torch.cuda.Event()
             area.event.record(self.stream)
@@ -219,9 +243,9 @@ class DevicePairLoader(PairLoader):
     touch, within its own budget."""
 
     def __init__(self, frames_dir, masks_dir, size, batch_size, seed, shuffle=True, horizontal_flip=False, rank=0,
-                 world=1, workers=16, cache_bytes=None, device="cuda", device_cache_bytes=None):
+                 world=1, workers=16, cache_bytes=None, device="cuda", device_cache_bytes=None, augment=None):
         super().__init__(frames_dir, masks_dir, size, batch_size, seed, shuffle, horizontal_flip, rank, world,
-                         workers, cache_bytes)
+                         workers, cache_bytes, augment)
         self.device = device
         self.pair_bytes = size[0] * size[1] * 4
         if device_cache_bytes is None:
@@ -238,9 +262,9 @@ class DevicePairLoader(PairLoader):
     def store(self):
         if self._store is None:
             if self.device is None:
-                self._store = _HostStore(self.book.slots, self.size)
+                self._store = _HostStore(self.book.slots, self.size, self.augment)
             else:
-                self._store = _DeviceStore(self.book.slots, self.size, self.local_batch, self.device)
+                self._store = _DeviceStore(self.book.slots, self.size, self.local_batch, self.device, self.augment)
         return self._store
 
     def __iter__(self):
@@ -254,8 +278,9 @@ class DevicePairLoader(PairLoader):
             raise ValueError(f"sample {i}: decoded to {f.shape}, {m.shape}, expected {tuple(self.size)}")
         return f, m
 
-    def load(self, idx, flips):
-        plan = self.book.plan(idx, [bool(flips[i]) for i in idx])
+    def load(self, idx, flips, records=None):
+        # with transform records the flip is in the record: the slot table is planned without flips
+        plan = self.book.plan(idx, [records is None and bool(flips[i]) for i in idx])
         staying = {i for i, _ in plan.new_resident}
         jobs = [(i, i not in staying) for i, _ in plan.uploads]
         if self.workers > 1 and len(jobs) > 1:
@@ -265,6 +290,6 @@ class DevicePairLoader(PairLoader):
             pairs = list(self._pool.map(lambda j: self._decode(*j), jobs))
         else:
             pairs = [self._decode(*j) for j in jobs]
-        x, y, self._event = self.store.batch(plan, pairs)
+        x, y, self._event = self.store.batch(plan, pairs, records)
         self.book.commit(plan)
         return x, y

@@ -1063,6 +1063,40 @@ def batch_gather_u8(src: Tensor, slots: Tensor, out: Tensor) -> Tensor:
     return out
 
 
+def batch_affine_u8(src: Tensor, slots: Tensor, xforms: Tensor, out: Tensor, order: int = 1,
+                    fill_constant: bool = False, cval: float = 0.0) -> Tensor:
+    """batch_gather_u8 with an affine warp: slots (b,) int32 are plain sample indices (clamped into
+    the cache on the device), xforms (b, 6) fp32 the transform record of each batch position
+    (augment.Augment.records: [m00 m01 o0 m10 m11 o1], the flip folded in).  order 0 nearest, 1
+    bilinear; fill_constant: pixels sampled outside the image take cval (0..255 units) instead of the
+    replicated border.  Bitwise augment.affine_u8_reference(src, slots, xforms, order, fill_constant,
+    cval)."""
+    _check_dt(src, "src", torch.uint8)
+    _check_dt(slots, "slots", torch.int32)
+    _check(xforms, "xforms")
+    _check(out, "out")
+    if src.dim() != 4 or src.shape[3] not in (1, 3):
+        raise ValueError(f"src: expected (n, h, w, 1 or 3) samples, got {tuple(src.shape)}")
+    n, h, w, c = (int(v) for v in src.shape)
+    if slots.dim() != 1:
+        raise ValueError(f"slots: expected shape (b,), got {tuple(slots.shape)}")
+    b = int(slots.shape[0])
+    if tuple(xforms.shape) != (b, 6):
+        raise ValueError(f"xforms: expected ({b}, 6), got {tuple(xforms.shape)}")
+    if tuple(out.shape) != (b, h, w, c):
+        raise ValueError(f"out: expected ({b}, {h}, {w}, {c}), got {tuple(out.shape)}")
+    if min(n, h, w, b) < 1:
+        raise ValueError(f"empty warp: {n} samples of {h}x{w}, {b} slots")
+    if h * w * c > 2 ** 31 - 1:
+        raise ValueError(f"a sample of {h}x{w}x{c} exceeds 2^31 bytes")
+    if order not in (0, 1):
+        raise ValueError(f"order must be 0 or 1, got {order!r}")
+    px = float(b * h * w * c)
+    _call("unet_batch_affine_u8", ((14.0 if order else 6.0) * px, (8.0 if order else 5.0) * px + 28.0 * b), _ptr(src), n,
+          h, w, c, _ptr(slots), _ptr(xforms), b, int(order), int(bool(fill_constant)), float(cval), _ptr(out), _stream())
+    return out
+
+
 def mask_resize(prob: Tensor, ytab: Tensor, xtab: Tensor, out: Tensor, threshold: float = 0.5) -> Tensor:
     """fp32 probabilities (h, w, ncls) of one image -> uint8 mask out (oh, ow): 255 where the
     bilinearly resized probability > threshold (ncls == 1), else the argmax class index; bitwise the
